@@ -58,7 +58,7 @@ static constexpr bool fuse_eq_zs() {
 #endif
 }
 
-extern "C" int mst_abi_version(void) { return 9; }
+extern "C" int mst_abi_version(void) { return 10; }
 #ifdef MST_DEV_PROBE  // developer probe (tools/sidestream_probe.py): an event recorded in the middle of the forward's launch sequence
 static hipEvent_t g_probe_ev = nullptr;
 static int g_probe_where = 0;

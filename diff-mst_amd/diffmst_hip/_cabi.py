@@ -25,7 +25,7 @@ NO_RANGE_CHECK = 0x400
 BWD_PREPARED = 0x800
 SPLIT_BATCH = 0x1000
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class ConsoleDesc(C.Structure):
@@ -145,6 +145,14 @@ SIGNATURES = {
     "mst_peak_normalize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "mst_peak_normalize_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _P]),
     "mst_peak_normalize_backward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _P]),
+    "mst_loudness_tables_bytes": (C.c_size_t, [C.c_int32]),
+    "mst_loudness_init_tables": (C.c_int, [C.c_int32, _P, _P]),
+    "mst_loudness_num_blocks": (C.c_int32, [C.c_int64, C.c_int32]),
+    "mst_loudness_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "mst_loudness_integrated": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P,
+                                          C.c_size_t, _P]),
+    "mst_loudness_normalize": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float,
+                                         _P, _P]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (C.c_int, [_P, _P]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

@@ -61,6 +61,142 @@ def batch_stereo_peak_normalize(x: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------------------------
+# Integrated loudness on the device (mst_loudness.hip).  BS.1770-4 as pyloudnorm.Meter computes it with its defaults;
+# PARITY UNPINNED: restated from pyloudnorm's published source, never run against the package.
+# ------------------------------------------------------------------------------------------------
+_LOUDNESS_TABLES = {}
+
+
+def _loudness_tables(device, sample_rate):
+    """Block boundaries, K-weighting coefficients and transition-matrix powers: built once per (device, rate)."""
+    key = (str(device), int(sample_rate))
+    t = _LOUDNESS_TABLES.get(key)
+    if t is None:
+        lib = _hip.lib()
+        nbytes = lib.mst_loudness_tables_bytes(int(sample_rate))
+        if nbytes == 0:
+            raise ValueError(f"unsupported sample rate {sample_rate} (the device meter needs at least 20500 Hz)")
+        t = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _hip.check(lib.mst_loudness_init_tables(int(sample_rate), _cabi.ptr(t), _hip.current_stream_ptr(device)),
+                       "mst_loudness_init_tables")
+        _LOUDNESS_TABLES[key] = t
+    return t
+
+
+def _forward_only(x, what):
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise NotImplementedError(f"{what} is forward-only (the reference never differentiates through the loudness meter); "
+                                  "detach the input or call it under torch.no_grad()")
+
+
+def _as_rows(x):
+    """``(..., channels, n)`` -> a ``(rows, channels, n)`` fp32 view with unit sample stride (copies only when it has to)."""
+    if x.dim() < 2:
+        raise ValueError("expected a (..., channels, n_samples) tensor")
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(-1) != 1 and x.shape[-1] > 1:
+        x = x.contiguous()
+    return x.reshape(-1, x.shape[-2], x.shape[-1])  # a view whenever the leading dimensions collapse
+
+
+def _check_audio(channels, n, sample_rate):
+    """pyloudnorm's ``valid_audio`` checks with its messages; raised before anything touches the device."""
+    if channels > 5:
+        raise ValueError("Audio must have five channels or less.")
+    if n < 0.4 * sample_rate:
+        raise ValueError("Audio must have length greater than the block size.")
+
+
+def _meter(x3, sample_rate, return_blocks):
+    lib = _hip.lib()
+    rows, chs, n = x3.shape
+    dev = x3.device
+    _check_audio(chs, n, sample_rate)
+    nblocks = lib.mst_loudness_num_blocks(n, int(sample_rate)) if rows > 0 and chs > 0 else 0
+    tables = _loudness_tables(dev, sample_rate)
+    nbytes = lib.mst_loudness_workspace_bytes(rows, chs, n, int(sample_rate))
+    if nbytes == 0 or nblocks == 0:
+        raise ValueError(f"unsupported loudness call: rows={rows}, channels={chs}, n_samples={n}, sample_rate={sample_rate}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lufs = torch.empty(rows, dtype=torch.float32, device=dev)
+    blocks = torch.empty(rows, nblocks, dtype=torch.float32, device=dev) if return_blocks else None
+    with torch.cuda.device(dev):
+        _hip.check(lib.mst_loudness_integrated(_cabi.ptr(x3), rows, chs, n, x3.stride(0), x3.stride(1), int(sample_rate),
+                                               _cabi.ptr(tables), _cabi.ptr(lufs), _cabi.ptr(blocks), _cabi.ptr(ws), nbytes,
+                                               _hip.current_stream_ptr(dev)), "mst_loudness_integrated")
+    return lufs, blocks
+
+
+def integrated_loudness(x: torch.Tensor, sample_rate: int = 44100, return_blocks: bool = False):
+    """Integrated loudness (LUFS) of ``x (..., channels, n)`` on the device -> tensor of shape ``(...)``; with
+    ``return_blocks`` also the loudness of every 0.4 s gating block, ``(..., num_blocks)``.  Channel weights 1, 1, 1, 1.41, 1.41;
+    ``-inf`` where no block passes the gates.  Nothing is read back: the call never synchronises with the host."""
+    x3 = _as_rows(x)
+    _check_audio(x3.shape[1], x3.shape[2], sample_rate)
+    _hip.require_cuda(x)
+    _forward_only(x, "integrated_loudness")
+    lufs, blocks = _meter(x3, sample_rate, return_blocks)
+    lead = x.shape[:-2]
+    if return_blocks:
+        return lufs.view(lead), blocks.view(*lead, blocks.shape[-1])
+    return lufs.view(lead)
+
+
+def loudness_normalize(x: torch.Tensor, target_lufs: float, sample_rate: int = 44100, floor_lufs=None):
+    """``y = x * 10^((target_lufs - L) / 20)`` with ``L`` the integrated loudness of every ``(channels, n)`` item of
+    ``x (..., channels, n)``, the gain formed on the device.  Returns ``(y, lufs (...), keep (...) bool)``, all on the device;
+    items below ``floor_lufs`` (and silent ones, ``L = -inf``) have ``keep = False`` and come back as zeros."""
+    x3 = _as_rows(x)
+    _check_audio(x3.shape[1], x3.shape[2], sample_rate)
+    _hip.require_cuda(x)
+    _forward_only(x, "loudness_normalize")
+    lufs, _ = _meter(x3, sample_rate, False)
+    y, keep = _apply_loudness_gain(x3, lufs, target_lufs, floor_lufs)
+    lead = x.shape[:-2]
+    return y.view(x.shape), lufs.view(lead), keep.view(lead)
+
+
+def _apply_loudness_gain(x3, lufs, target_lufs, floor_lufs):
+    lib = _hip.lib()
+    rows, chs, n = x3.shape
+    dev = x3.device
+    y = torch.empty(rows, chs, n, dtype=torch.float32, device=dev)
+    keep = torch.empty(rows, dtype=torch.uint8, device=dev)
+    floor = float("-inf") if floor_lufs is None else float(floor_lufs)
+    with torch.cuda.device(dev):
+        _hip.check(lib.mst_loudness_normalize(_cabi.ptr(x3), _cabi.ptr(y), _cabi.ptr(lufs), rows, chs, n, x3.stride(0), x3.stride(1),
+                                              float(target_lufs), floor, _cabi.ptr(keep), _hip.current_stream_ptr(dev)),
+                   "mst_loudness_normalize")
+    return y, keep.bool()
+
+
+class LoudnessMeter:
+    """Drop-in for ``pyloudnorm.Meter(rate)`` where only ``integrated_loudness`` is used (defaults: K-weighting, 0.4 s blocks):
+    ``integrated_loudness(data)`` takes what pyloudnorm takes - a numpy array or host tensor ``(n,)`` / ``(n, channels)`` -
+    runs the device meter on it and returns a Python ``float``.  ``run_diffmst(..., loudness_fn=LoudnessMeter(44100)
+    .integrated_loudness)`` works on a machine without pyloudnorm."""
+
+    def __init__(self, rate: int):
+        self.rate = int(rate)
+
+    def integrated_loudness(self, data) -> float:
+        x = torch.as_tensor(data)
+        if x.dim() == 1:
+            x = x.unsqueeze(1)
+        if x.dim() != 2:
+            raise ValueError("expected (n_samples,) or (n_samples, channels) audio")
+        if not x.is_floating_point():
+            raise ValueError("Data must be floating point.")  # pyloudnorm's message
+        _check_audio(x.shape[1], x.shape[0], self.rate)
+        dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        x = x.detach().to(device=dev, dtype=torch.float32).t().contiguous()  # (channels, n)
+        return float(integrated_loudness(x, self.rate).item())
+
+
+# ------------------------------------------------------------------------------------------------
 # Inference driver (reference mst/utils.py:32-258): forward-only, batch 1, long songs
 # ------------------------------------------------------------------------------------------------
 ANALYSIS_LEN = 262144  # reference mst/utils.py:66
@@ -72,7 +208,8 @@ def _default_loudness_fn(sample_rate=44100):
     try:
         import pyloudnorm as pyln
     except ImportError as e:  # fail loudly: there is no silent stand-in for BS.1770 loudness
-        raise ImportError("run_diffmst needs pyloudnorm (reference requirements.txt) or an explicit loudness_fn(ndarray (n, ch)) -> LUFS") from e
+        raise ImportError("run_diffmst needs pyloudnorm (reference requirements.txt), an explicit loudness_fn(ndarray (n, ch)) -> LUFS, "
+                          "or loudness_fn=\"device\" for this package's own meter") from e
     return pyln.Meter(sample_rate).integrated_loudness
 
 
@@ -90,7 +227,9 @@ def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module,
     writes through a view); model and console windows run on ``device`` (default: the model's device if it is a GPU, else the
     current GPU; a model still on the host - what ``load_diffmst`` returns - is moved there with ``model.to(device)``) and
     ``pred_mix`` comes back on ``tracks.device``; ``loudness_fn(ndarray (n, 1)) -> float`` replaces the
-    pyloudnorm meter where that package is absent (it is host-side in the reference too)."""
+    pyloudnorm meter where that package is absent (it is host-side in the reference too); ``loudness_fn="device"`` measures and
+    normalises on the device instead (``integrated_loudness`` / ``loudness_normalize`` above - BS.1770 as pyloudnorm computes it,
+    parity unpinned): one meter call over all tracks, and the only host read is the mask of the tracks that survive."""
     if tracks.dim() != 3 or tracks.shape[0] != 1:
         raise ValueError("tracks must be (1, num_tracks, seq_len)")  # the reference's squeeze(0) / zeros(1, 2, n) fix bs = 1
     if loudness_fn is None:
@@ -111,6 +250,35 @@ def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module,
         analysis_tracks = tracks
     analysis_ref = ref[..., ref_start_idx:ref_start_idx + ANALYSIS_LEN] if ref.shape[-1] >= ANALYSIS_LEN else ref
 
+    if isinstance(loudness_fn, str):
+        if loudness_fn != "device":
+            raise ValueError('loudness_fn must be a callable, None or "device"')
+        norm_tracks, norm_analysis = _normalize_tracks_on_device(tracks, n, track_start_idx, device, verbose)
+    else:
+        norm_tracks, norm_analysis = _normalize_tracks_on_host(tracks, analysis_tracks, loudness_fn, device, verbose)
+    return _mix_windows(tracks, norm_tracks, norm_analysis, analysis_ref, model, mix_console, device, n)
+
+
+def _normalize_tracks_on_device(tracks, n, track_start_idx, device, verbose):
+    """-48 LUFS from the analysis crop, -80 LUFS floor, all tracks in one meter call; the host reads the keep mask only."""
+    dev_tracks = tracks.detach().to(device=device, dtype=torch.float32)[0].unsqueeze(1)  # (T, 1, n): rows = tracks, mono
+    crop = dev_tracks[..., track_start_idx:track_start_idx + ANALYSIS_LEN] if n >= ANALYSIS_LEN else dev_tracks
+    lufs, _ = _meter(crop, 44100, False)  # a last-dimension slice: strided rows, no copy
+    y, keep = _apply_loudness_gain(dev_tracks, lufs, -48.0, -80.0)
+    keep = keep.cpu()  # the number of surviving tracks shapes the model's input: the one inherent synchronisation
+    if verbose:
+        for t in (~keep).nonzero().flatten().tolist():
+            print(f"Skipping track {t} due to low loudness {float(lufs[t])}.")
+    if not bool(keep.any()):
+        raise RuntimeError("every track is below -80 LUFS")
+    y = y.view(1, -1, n)
+    if not bool(keep.all()):
+        y = y.index_select(1, keep.nonzero().flatten().to(device))
+    norm_analysis = y[..., track_start_idx:track_start_idx + ANALYSIS_LEN].contiguous() if n >= ANALYSIS_LEN else y
+    return y, norm_analysis
+
+
+def _normalize_tracks_on_host(tracks, analysis_tracks, loudness_fn, device, verbose):
     # loudness-normalise to -48 LUFS (host side, like the reference: the meter works on numpy)
     keep, gains = [], []
     host_analysis = analysis_tracks.detach().float().cpu()
@@ -128,7 +296,10 @@ def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module,
     g = torch.tensor(gains, dtype=torch.float32).view(1, -1, 1)
     norm_tracks = (tracks.detach().float().index_select(1, idx) * g.to(tracks.device)).to(device).contiguous()
     norm_analysis = (analysis_tracks.detach().float().index_select(1, idx) * g.to(tracks.device)).to(device).contiguous()
+    return norm_tracks, norm_analysis
 
+
+def _mix_windows(tracks, norm_tracks, norm_analysis, analysis_ref, model, mix_console, device, n):
     # ---- one parameter estimate from the analysis audio
     pred_track_params, pred_fx_bus_params, pred_master_bus_params = model(norm_analysis, analysis_ref.float().to(device))
 

@@ -255,6 +255,36 @@ int mst_peak_normalize_backward(const float* x, const float* grad_y, float* grad
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Integrated loudness (ITU-R BS.1770-4 as pyloudnorm.Meter(rate).integrated_loudness computes it with its defaults: K-weighting,
+ * 0.4 s gating blocks with 75 % overlap, absolute gate -70 LUFS, relative gate -10 LU) - the meter the reference's inference
+ * driver, data pipeline and evaluation scripts normalise with (mst/utils.py:67,93; mst/dataloader.py:66).  PARITY UNPINNED: a
+ * restatement of pyloudnorm's published source, not checked against the package.
+ *   x               `rows` signals of `channels` (1..5, weights 1 1 1 1.41 1.41) channels of n_samples fp32 samples, unit sample
+ *                   stride, row_stride / channel_stride elements between rows / channels (a last-dimension crop needs no copy)
+ *   tables          mst_loudness_tables_bytes(rate) bytes filled once by mst_loudness_init_tables(rate); they open with 4096 int32
+ *                   block boundaries  bound[k] = int(0.4 * (k * 0.25) * rate)  evaluated on the host in float64 exactly as
+ *                   pyloudnorm writes it (gating block j = samples [bound[j], bound[j + 4])), followed by the filter coefficients
+ *                   and the powers of the filter's state-transition matrix
+ *   lufs            (rows) fp32; -inf when no block passes the gates
+ *   block_loudness  NULL or (rows, mst_loudness_num_blocks(n_samples, rate)) fp32, the loudness l_j of every gating block
+ * mst_loudness_num_blocks / mst_loudness_workspace_bytes return 0 for what is not supported: signals shorter than one gating
+ * block (pyloudnorm raises there; n_samples == 0.4 * rate is one block), more than 4092 blocks, sample rates below 20500 Hz.
+ * Four launches, deterministic (no floating-point atomics), no host synchronisation. */
+size_t mst_loudness_tables_bytes(int32_t sample_rate);
+int mst_loudness_init_tables(int32_t sample_rate, void* tables, void* stream);
+int32_t mst_loudness_num_blocks(int64_t n_samples, int32_t sample_rate);
+size_t mst_loudness_workspace_bytes(int32_t rows, int32_t channels, int64_t n_samples, int32_t sample_rate);
+int mst_loudness_integrated(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride,
+                            int64_t channel_stride, int32_t sample_rate, const void* tables, float* lufs, float* block_loudness,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* y[row] = x[row] * 10^((target_lufs - lufs[row]) / 20), the gain formed on the device; x strided as above, y dense
+ * (rows, channels, n_samples).  keep (rows) bytes or NULL: 1 where lufs[row] >= floor_lufs and finite (-inf floor: every row
+ * that has a loudness); rows that are not kept are written as zeros. */
+int mst_loudness_normalize(const float* x, float* y, const float* lufs, int32_t rows, int32_t channels, int64_t n_samples,
+                           int64_t row_stride, int64_t channel_stride, float target_lufs, float floor_lufs, uint8_t* keep,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
  * (:127-195) and the 24-band Bark spectrum of mid/side (:62-124; STFT 32768 / hop 8192 / Hann).
