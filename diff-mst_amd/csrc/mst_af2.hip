@@ -26,21 +26,14 @@ constexpr int kAf2Lanes = 512;
 #endif
 
 // |X| and g / |X| on the hardware's 1-ulp v_sqrt_f32 / v_rsq_f32 (the correctly rounded sqrtf and '/' are 10 + 11 instructions per bin
-// with a denormal guard; -DMST_AF_PRECISE_MAG=1 restores them).  |X|^2 below 1e-30 - |X| < 1e-15, far under fp32 round-off of any
+// with a denormal guard).  |X|^2 below 1e-30 - |X| < 1e-15, far under fp32 round-off of any
 // audible frame - counts as zero in the gradient, as |X| = 0 did.
-#ifndef MST_AF_PRECISE_MAG
-#define MST_AF_PRECISE_MAG 0
-#endif
 __device__ __forceinline__ float af_mag(float2 X) {
     const float p2 = X.x * X.x + X.y * X.y;
-    return MST_AF_PRECISE_MAG ? sqrtf(p2) : __builtin_amdgcn_sqrtf(p2);
+    return __builtin_amdgcn_sqrtf(p2);
 }
 __device__ __forceinline__ float af_over_mag(float g, float2 X) {
     const float p2 = X.x * X.x + X.y * X.y;
-    if (MST_AF_PRECISE_MAG) {
-        const float m = sqrtf(p2);
-        return m > 0.f ? g / m : 0.f;
-    }
     return p2 > 1e-30f ? g * __builtin_amdgcn_rsqf(p2) : 0.f;
 }
 // W_32^t = (cos, -sin)(2 pi t / 32), t < 16: W_16384^(lane + 512 t) = W_16384^lane W_32^t
@@ -171,11 +164,8 @@ __global__ __launch_bounds__(kAf2Lanes, MST_AF2_W) void k_af2_bark_fwd(AfArgs a)
     // next to each other: workgroup id L lands on XCD L % 8 (mst_common.h: row_block_xcd), and with the plain (strip, signal, half) grid
     // the four sat on four XCDs - every frame (256 KB) crossed the fabric four times, 2.2 GB per launch at bs 32, against an L2 that
     // 64 resident workgroups x 256 KB overflow anyway.  Any other batch size keeps the plain walk; the result does not depend on it.
-#ifndef MST_AF2_XCD
-#define MST_AF2_XCD 1
-#endif
     int grp = blockIdx.x, sgn = blockIdx.y, half = blockIdx.z;
-    if (MST_AF2_XCD && (2 * a.bs) % 8 == 0) {
+    if ((2 * a.bs) % 8 == 0) {
         const int L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), xcd = L & 7, k = L >> 3;
         const int W = 4 * a.n_groups, src = (k / W) * 8 + xcd, rem = k % W, var = rem & 3;  // src = (pred | target, batch item)
         grp = rem >> 2;
@@ -266,7 +256,7 @@ template <int HALF>
 __global__ __launch_bounds__(kAf2Lanes, MST_AF2_W_BWD) void k_af2_bark_bwd(AfArgs a) {
     __shared__ __attribute__((aligned(16))) float2 buf[2][AfS::SLOTS];
     int f = blockIdx.x, s = blockIdx.y;  // s < 2*bs
-    if (MST_AF2_XCD && a.bs % 8 == 0) {
+    if (a.bs % 8 == 0) {
         // the 2 x n_frames workgroups of one batch item (mid and side of every frame: frames overlap 4x) on one XCD, frames ascending: the
         // resident set of an XCD is then a window of ~32 consecutive frames of one stereo pair = 2 MB, which its L2 holds
         const int L = blockIdx.x + gridDim.x * blockIdx.y, xcd = L & 7, k = L >> 3, per = 2 * a.n_frames;

@@ -19,8 +19,7 @@
 //                squares that BatchNorm needs ride in the epilogue (fp32 accumulators, before any rounding).
 //                The data gradient is the same kernel on (dY, W^T rotated by 180 degrees) - see k_prep_weights.
 // k_conv_igemm3 / k_conv_igemm4   the bf16 production form of that GEMM: tiles fetched by LDS-direct loads into a ring with counted
-//                waits (3), the three taps of an image row sharing one activation segment (4).  k_conv_igemm stays for fp32 operands
-//                and as the register-staged A/B baseline (-DMST_CONV_NO_GLDS).
+//                waits (3), the three taps of an image row sharing one activation segment (4).  k_conv_igemm stays for fp32 operands.
 // k_conv_wgrad3 / k_conv_wgrad4   bf16 weight gradient on the same loader + ds_read_b64_tr_b16 fragments; one tap (3) or all nine (4)
 //                per workgroup.
 // k_conv_wgrad   dW[co][tap][ci] = sum_pixel dY[pixel][co] X[pixel + tap][ci]: K = pixels, which is the STRIDED axis of both
@@ -34,9 +33,6 @@
 
 namespace mst {
 
-#ifndef MST_CONV_ABLATE
-#define MST_CONV_ABLATE 0
-#endif
 #ifndef MST_CONV_X3_STAGES
 #define MST_CONV_X3_STAGES 2  // LDS stages of the bf16x3 implicit GEMM
 #endif
@@ -44,7 +40,7 @@ namespace mst {
 #define MST_CONV_X3_BK 32     // K per staged tile of the bf16x3 implicit GEMM (32 | 64)
 #endif
 #ifndef MST_CONV_LDS_STAGES
-#define MST_CONV_LDS_STAGES 2  // A/B switch: 1 = one LDS stage, two barriers per K step
+#define MST_CONV_LDS_STAGES 2  // 1 = one LDS stage, two barriers per K step
 #endif
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -194,9 +190,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(ConvArgs a) {  // 2: up t
     }
     uint4 rw[WCH], rx[XCH];
     auto gload_to = [&](uint4* rx, uint4* rw, int tap, int c0) {
-#if MST_CONV_ABLATE & 1  // timing diagnostics only (wrong results): no global loads inside the K loop
-        if (tap > 0 || c0 > 0) return;
-#endif
         const int dh = tap / 3 - 1, dw = tap % 3 - 1;
         const int64_t shift = ((int64_t)dh * W + dw) * Cin + c0;
 #pragma unroll
@@ -226,9 +219,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm(ConvArgs a) {  // 2: up t
         for (int q = 0; q < WCH; ++q) *reinterpret_cast<uint4*>(&sW[woff[q]]) = rw[q];
     };
     auto multiply = [&](const T* sX, const T* sW) {
-#if MST_CONV_ABLATE & 2  // no LDS reads, no MFMAs
-        return;
-#endif
         if constexpr (sizeof(T) == 2) {
 #pragma unroll
             for (int ks = 0; ks < BK / 32; ++ks) {
@@ -392,9 +382,6 @@ template <int N> __device__ __forceinline__ void lds_frags_landed(u32x4 (&r)[N])
 #ifndef MST_CONV_GLDS_STAGES
 #define MST_CONV_GLDS_STAGES 3
 #endif
-#ifndef MST_CONV_XCD_REMAP
-#define MST_CONV_XCD_REMAP 1  // pixel tiles in eight contiguous ranges, one per XCD (neighbouring image rows share an L2)
-#endif
 template <int BC, int BP, int NS>
 __global__ __launch_bounds__(256, 2) void k_conv_igemm3(ConvArgs a) {
     constexpr int BK = 32, MT = BC / 32, NT = BP / 32;
@@ -408,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm3(ConvArgs a) {
     const int g = lane >> 4, li = lane & 15;
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
     int bx = blockIdx.x;
-    if (MST_CONV_XCD_REMAP) {  // workgroup ids go round-robin over the 8 XCDs: give XCD j the j-th contiguous range of tiles
+    {  // workgroup ids go round-robin over the 8 XCDs: give XCD j the j-th contiguous range of tiles
         const int gx = gridDim.x, q = gx >> 3, r = gx & 7, xcd = bx & 7, idx = bx >> 3;
         bx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
@@ -573,7 +560,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_igemm4(ConvArgs a) {
     const int g = lane >> 4, li = lane & 15;
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout, HW = H * W;
     int bx = blockIdx.x;
-    if (MST_CONV_XCD_REMAP) {
+    {
         const int gx = gridDim.x, q = gx >> 3, r = gx & 7, xcd = bx & 7, idx = bx >> 3;
         bx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
@@ -792,13 +779,6 @@ __global__ __launch_bounds__(256) void k_conv_splitk_reduce(const float* __restr
         }
     }
 }
-static constexpr bool conv3_enabled() {
-#ifdef MST_CONV_NO_GLDS
-    return false;  // A/B switch: register-staged k_conv_igemm
-#else
-    return true;
-#endif
-}
 static int conv_csplit(int N, int H, int W, int Cin, int Cout) {
     const int tiles = conv_pixel_tiles(N, H, W), bc = Cout % 128 == 0 ? 128 : 64, wgs = tiles * (Cout / bc);
     if (wgs >= 512) return 0;
@@ -826,29 +806,24 @@ int launch_conv3x3(int precision, ConvArgs a, hipStream_t s, float* kpart, size_
 #define MST_CONV_FAT_MIN 1024  // workgroups from which the 256-pixel tile is used
 #endif
     const bool fat_ok = precision == 0 && !a.csplit && a.Cout % 128 == 0 && (int64_t)tiles2 * (a.Cout / 128) >= MST_CONV_FAT_MIN;
-#ifndef MST_CONV_TAPROW
-#define MST_CONV_TAPROW 1  // A/B switch: 0 = k_conv_igemm3 everywhere
-#endif
-    if (MST_CONV_TAPROW && conv3_enabled() && precision == 0 && !a.csplit && (int64_t)tiles2 * (a.Cout / (a.Cout % 128 == 0 ? 128 : 64)) >= MST_CONV_FAT_MIN) {
+    if (precision == 0 && !a.csplit && (int64_t)tiles2 * (a.Cout / (a.Cout % 128 == 0 ? 128 : 64)) >= MST_CONV_FAT_MIN) {
         if (a.Cout % 128 == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm4<128, 256>), dim3(tiles2, a.Cout / 128), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm4<64, 256>), dim3(tiles2, a.Cout / 64), dim3(256), 0, s, a);
         return tiles2;
     }
-    if (fat_ok && conv3_enabled()) {
+    if (fat_ok) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm3<128, 256, MST_CONV_GLDS_STAGES>), dim3(tiles2, a.Cout / 128), dim3(256), 0, s, a);
         return tiles2;
     }
     if (a.Cout % 128 == 0) {
         const dim3 grid(tiles, a.Cout / 128, gz);
-        if (precision == 0 && conv3_enabled()) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm3<128, 128, MST_CONV_GLDS_STAGES>), grid, dim3(256), 0, s, a);
-        else if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<bf16_t, 128, 64>), grid, dim3(256), 0, s, a);
+        if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm3<128, 128, MST_CONV_GLDS_STAGES>), grid, dim3(256), 0, s, a);
         else if (precision == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<float, 128, MST_CONV_X3_BK, 3>), grid, dim3(256), 0, s, a);
         else if (precision == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<float, 128, MST_CONV_X3_BK, 6>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<float, 128, 32>), grid, dim3(256), 0, s, a);
     } else {
         const dim3 grid(tiles, a.Cout / 64, gz);
-        if (precision == 0 && conv3_enabled()) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm3<64, 128, MST_CONV_GLDS_STAGES>), grid, dim3(256), 0, s, a);
-        else if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<bf16_t, 64, 32>), grid, dim3(256), 0, s, a);
+        if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm3<64, 128, MST_CONV_GLDS_STAGES>), grid, dim3(256), 0, s, a);
         else if (precision == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<float, 64, MST_CONV_X3_BK, 3>), grid, dim3(256), 0, s, a);
         else if (precision == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<float, 64, MST_CONV_X3_BK, 6>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_igemm<float, 64, 32>), grid, dim3(256), 0, s, a);
@@ -1324,11 +1299,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad4(WgradArgs a) {
     }
 }
 bool conv_wgrad_nine_taps(int precision, int W, int Cin, int Cout) {
-#ifdef MST_CONV_NO_WGRAD4
-    return false;  // A/B switch
-#else
-    return precision == 0 && conv3_enabled() && W >= 64 && Cin % 64 == 0 && Cout % 64 == 0;
-#endif
+    return precision == 0 && W >= 64 && Cin % 64 == 0 && Cout % 64 == 0;
 }
 
 void launch_conv_wgrad(int precision, const WgradArgs& a, hipStream_t s) {
@@ -1346,16 +1317,14 @@ void launch_conv_wgrad(int precision, const WgradArgs& a, hipStream_t s) {
     } else if (a.Cin % 128 == 0 && a.Cout % 128 == 0) {
         const dim3 grid((a.Cout / 128) * (a.Cin / 128), 9, a.splits);
         const dim3 grid3((a.Cout / 128) * (a.Cin / 128) * 9 * ((a.splits + 7) / 8) * 8);
-        if (precision == 0 && conv3_enabled()) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad3<128, 128, MST_CONV_GLDS_STAGES>), grid3, dim3(256), 0, s, a);
-        else if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<bf16_t, 128, 128, false>), grid, dim3(256), 0, s, a);
+        if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad3<128, 128, MST_CONV_GLDS_STAGES>), grid3, dim3(256), 0, s, a);
         else if (precision == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<float, 128, 128, false, 3>), grid, dim3(256), 0, s, a);
         else if (precision == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<float, 128, 128, false, 6>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<float, 128, 128, false>), grid, dim3(256), 0, s, a);
     } else {
         const dim3 grid((a.Cout / 64) * (a.Cin / 64), 9, a.splits);
         const dim3 grid3((a.Cout / 64) * (a.Cin / 64) * 9 * ((a.splits + 7) / 8) * 8);
-        if (precision == 0 && conv3_enabled()) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad3<64, 64, MST_CONV_GLDS_STAGES>), grid3, dim3(256), 0, s, a);
-        else if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<bf16_t, 64, 64, false>), grid, dim3(256), 0, s, a);
+        if (precision == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad3<64, 64, MST_CONV_GLDS_STAGES>), grid3, dim3(256), 0, s, a);
         else if (precision == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<float, 64, 64, false, 3>), grid, dim3(256), 0, s, a);
         else if (precision == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<float, 64, 64, false, 6>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_wgrad<float, 64, 64, false>), grid, dim3(256), 0, s, a);

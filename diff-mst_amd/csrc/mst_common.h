@@ -9,9 +9,6 @@
 
 namespace mst {
 
-#ifndef MST_FUSE_COEFGRAD
-#define MST_FUSE_COEFGRAD 1  // the track rows' coefficient-gradient sums are made inside k_comp_bwd_run (A/B switch: 0 = k_coefgrad for every row)
-#endif
 constexpr int kSections = 6;           // low shelf, 4 peaking, high shelf (reference mst/modules.py:125-143)
 constexpr int kStates = 2 * kSections; // DF2T state of the whole cascade
 #ifndef MST_COMP_WG
@@ -99,13 +96,10 @@ __device__ __forceinline__ float biquad_step<float>(float x, const float* c, flo
 }
 
 // forward cascade, state st[2k], st[2k+1] for section k
-#ifndef MST_DBG_SECTIONS
-#define MST_DBG_SECTIONS kSections  // timing diagnostics only: fewer sections = less math, wrong results
-#endif
 template <typename T>
 __device__ __forceinline__ T cascade_step(T x, const T* c, T* st) {
 #pragma unroll
-    for (int k = 0; k < MST_DBG_SECTIONS; ++k) x = biquad_step<T>(x, c + 5 * k, st[2 * k], st[2 * k + 1]);
+    for (int k = 0; k < kSections; ++k) x = biquad_step<T>(x, c + 5 * k, st[2 * k], st[2 * k + 1]);
     return x;
 }
 
@@ -188,7 +182,7 @@ __device__ __forceinline__ void group_lds_sync() {
 // Sum over the 64 lanes of a wave, the same value returned to every lane.  Six DPP additions (row shifts by 1, 2, 4, 8 leave
 // each 16-lane row's total in its last lane, two row broadcasts carry the totals into lane 63) and one v_readlane, all
 // full-rate VALU work - `v += __shfl_xor(v, m)` compiles to six ds_bpermute_b32 round trips through the LDS crossbar
-// (180 of them closed every k_coefgrad tile).  Fixed order: results are reproducible.
+// (180 of them closed every tile of the round-2 coefficient-gradient kernel).  Fixed order: results are reproducible.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_add(float v) {
     return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
@@ -245,9 +239,6 @@ typedef unsigned long long gran_t;
 // within an L2 hit.  A reader polls both; a copy that shows the tag is the value (one 8-byte store each), whichever path it took,
 // so the result never depends on where the workgroups were placed - only the latency does, and the grids that exchange granules
 // are walked so that the blocks of one row share an XCD (row_block_xcd).
-#ifndef MST_GRAN_NEAR
-#define MST_GRAN_NEAR 1
-#endif
 // Status code a kernel raises (atomic max into the call's status word) when a bounded wait gives up: the values the launch wrote are
 // poisoned (NaN) and the host side turns the code into an error (diffmst_hip/_desc.py: status_to_error) - larger than every
 // range-check code (1000 - index - 1), so it survives the max.
@@ -262,11 +253,11 @@ __device__ __forceinline__ void gran_publish(gran_t* g, int64_t near_off, float 
     return;
 #endif
     const gran_t x = ((gran_t)1 << 32) | (gran_t)(unsigned)__float_as_int(v);
-    if (MST_GRAN_NEAR && near_off) __hip_atomic_store(g + near_off, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (near_off) __hip_atomic_store(g + near_off, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __hip_atomic_store(g, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ float gran_wait(const gran_t* g, int64_t near_off, int32_t* status = nullptr) {
-    const bool near = MST_GRAN_NEAR && near_off;
+    const bool near = near_off;
     gran_t x = gran_load(near ? g + near_off : g);
     for (int spins = 0; (x >> 32) != 1; ++spins) {
         if (spins >= MST_GRAN_SPINS) {
@@ -300,7 +291,7 @@ __device__ __forceinline__ void gran_read_vec(const gran_t* g, int64_t near_off,
 #pragma unroll
     for (int d = 0; d < NV; ++d) out[d] = 0.0f;
     if (!active) return;
-    const bool has_near = MST_GRAN_NEAR && near_off;
+    const bool has_near = near_off;
     bool use_near = has_near;
     gran_t x[NV];
     for (int spins = 0;; ++spins) {
@@ -331,20 +322,15 @@ __device__ __forceinline__ void gran_read_vec(const gran_t* g, int64_t near_off,
 // `group` > 1: rows come in groups (the tracks of one mix) that read the same shared data (the bus cotangent of that mix): the whole
 // group is kept on one XCD and its rows are interleaved block by block, so that the shared block is fetched once per XCD instead of
 // once per row (with row r on XCD r % 8 the eight tracks of a mix sat on eight XCDs: 8 x 16 MB of bus cotangent over the fabric).
-__device__ __forceinline__ void row_block_xcd(int& row, int& step, int group = 1, int rows = 0, int skip_rows = 0, int lin = -1) {
-    // rows: 0 = the whole grid; skip_rows: grid rows in FRONT of the mapped ones that belong to another role of the launch;
-    // lin >= 0: the workgroup's index among the mapped ones, handed over by a caller that interleaves another role (same residue mod 8
-    // as its workgroup id, so that it still names the XCD)
+__device__ __forceinline__ void row_block_xcd(int& row, int& step, int group = 1, int rows = 0, int skip_rows = 0) {
+    // rows: 0 = the whole grid; skip_rows: grid rows in FRONT of the mapped ones that belong to another role of the launch
     const int nblk = gridDim.x;
     if (rows <= 0) rows = gridDim.y - skip_rows;
-    if (group >= 1 && rows % (8 * group) == 0 && (lin >= 0 || (nblk * skip_rows) % 8 == 0)) {
-        const int L = lin >= 0 ? lin : blockIdx.x + nblk * ((int)blockIdx.y - skip_rows), xcd = L & 7, k = L >> 3;
+    if (group >= 1 && rows % (8 * group) == 0 && (nblk * skip_rows) % 8 == 0) {
+        const int L = blockIdx.x + nblk * ((int)blockIdx.y - skip_rows), xcd = L & 7, k = L >> 3;
         const int per_group = group * nblk, gi = k / per_group, rem = k % per_group;
         row = (gi * 8 + xcd) * group + rem % group;
         step = rem / group;
-    } else if (lin >= 0) {
-        row = lin / nblk;
-        step = lin % nblk;
     } else {
         row = blockIdx.y - skip_rows;
         step = blockIdx.x;
@@ -358,7 +344,7 @@ struct Layout {
     int ncE, ncE_pad;        // EQ lane-chunks per signal row (pad to kWG)
     int ncC, ncC_pad;        // compressor lane-chunks per row
     int nblkE, nblkC;        // workgroups per row in EQ / compressor kernels
-    int nblkEt;              // coefficient-gradient partial rows per signal row: nblkC when k_comp_bwd_run makes them (MST_FUSE_COEFGRAD), else nblkE
+    int nblkEt;              // coefficient-gradient partial rows per signal row: nblkC (k_comp_bwd_run makes them)
     int KE, KC;              // chunks per scan thread
     int ntE;                 // 4096-sample EQ tiles per row
     int eq1;                 // 1: EQ carries scanned inside the zs / run kernels, 0: separate carry-scan kernel
@@ -396,7 +382,7 @@ struct Layout {
 };
 
 // floats between consecutive signal rows of the workspace arrays (u, g_s, bus, du ...): the row length rounded to 16 bytes, plus
-// MST_ROW_PAD floats (A/B switch: rows exactly 2^k bytes apart put the same block of every row on the same memory channel)
+// MST_ROW_PAD floats (rows exactly 2^k bytes apart put the same block of every row on the same memory channel)
 #ifndef MST_ROW_PAD
 #define MST_ROW_PAD 0
 #endif
@@ -414,7 +400,7 @@ inline Layout make_layout(const mst_console_desc* d) {
     L.ncC_pad = (int)round_up(L.ncC, kWG);
     L.nblkE = L.ncE_pad / kEqWG;
     L.nblkC = L.ncC_pad / kWG;
-    L.nblkEt = MST_FUSE_COEFGRAD ? L.nblkC : L.nblkE;
+    L.nblkEt = L.nblkC;
     L.KE = (L.ncE + kScanThreads - 1) / kScanThreads;
     if (L.KE > 8) L.KE = (int)round_up(L.KE, 8);  // whole 8-chunk sub-spans: aligned 16-byte state accesses in k_scan
     L.KC = (L.ncC + kScanThreads - 1) / kScanThreads;
@@ -424,12 +410,7 @@ inline Layout make_layout(const mst_console_desc* d) {
         int sh = 0;
         while ((L.KE << sh) < 64) ++sh;
         const bool pow2 = (L.KE << sh) == 64;
-#ifdef MST_APSCAN_SEPARATE
-        const bool on = false;
-#else
-        const bool on = true;
-#endif
-        L.apscan_fwd = (on && L.eq1 && pow2 && (d->flags & MST_USE_MASTER_BUS) && (d->flags & MST_SAVE_FOR_BACKWARD)) ? 1 : 0;
+        L.apscan_fwd = (L.eq1 && pow2 && (d->flags & MST_USE_MASTER_BUS) && (d->flags & MST_SAVE_FOR_BACKWARD)) ? 1 : 0;
         L.apscan_sh = sh;
     }
     int64_t o = 0;

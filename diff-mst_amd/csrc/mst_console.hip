@@ -2,6 +2,7 @@
 // launch sequences behind them.  No allocation, no host sync: everything is enqueued on the
 // caller's stream over the caller's workspace.
 #include "mst_kernels.h"
+#include "mst_dev.h"
 
 namespace mst {
 static int check_desc(const mst_console_desc* d) {
@@ -20,50 +21,8 @@ static int check_desc(const mst_console_desc* d) {
 
 using namespace mst;
 
-// build-time A/B switch (-DMST_ALLPOLE_SEPARATE): keep the all-pole zero-state pass as its own backward kernel
-static constexpr bool fuse_allpole() {
-#ifdef MST_ALLPOLE_SEPARATE
-    return false;
-#else
-    return true;
-#endif
-}
-
-// build-time A/B switch (-DMST_COMP_ZS_SEPARATE): the smoother's zero-state passes as launches of their own (k_comp_zs<2>, k_comp_bwd_zs)
-// instead of block aggregates exchanged inside the run launches (mst_common.h: granules)
-static constexpr bool fuse_comp_zs() {
-#ifdef MST_COMP_ZS_SEPARATE
-    return false;
-#else
-    return true;
-#endif
-}
-
-// build-time A/B switch (-DMST_EQ_ZS_VALU): zero-state EQ passes on the vector ALU (round-2 kernels) instead of the matrix pipe
-static constexpr bool mfma_zs() {
-#ifdef MST_EQ_ZS_VALU
-    return false;
-#else
-    return true;
-#endif
-}
-
-// build-time A/B switch (-DMST_EQ_ZS_SEPARATE): the EQ's zero-state passes as launches of their own (k_eq_zs_mfma) instead of inside the
-// run launches (ZsIn, mst_kernels.h)
-static constexpr bool fuse_eq_zs() {
-#ifdef MST_EQ_ZS_SEPARATE
-    return false;
-#else
-    return true;
-#endif
-}
-
 extern "C" int mst_abi_version(void) { return 10; }
-#ifdef MST_DEV_PROBE  // developer probe (tools/sidestream_probe.py): an event recorded in the middle of the forward's launch sequence
-static hipEvent_t g_probe_ev = nullptr;
-static int g_probe_where = 0;
-extern "C" void mst_debug_set_mid_event(void* ev, int where) { g_probe_ev = (hipEvent_t)ev; g_probe_where = where; }
-#endif
+MST_DEV_PROBE_STATE  // developer probe, mst_dev.h (nothing in a default build)
 
 extern "C" size_t mst_console_fx_tables_bytes(void) { return (size_t)8192 * 2 * sizeof(float); }
 extern "C" int mst_console_fx_init_tables(void* tables, void* stream) {
@@ -168,9 +127,7 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
         (void)hipMemcpyAsync(status_host, status, sizeof(int32_t), hipMemcpyDeviceToHost, stream);
         if (status_event) (void)hipEventRecord((hipEvent_t)status_event, stream);
     }
-#ifdef MST_DEV_PROBE
-    if (g_probe_ev && g_probe_where == 0) (void)hipEventRecord(g_probe_ev, stream);
-#endif
+    MST_DEV_PROBE_AT(0, stream);
 
     // ---- tracks: EQ (zs -> carry scan -> run), compressor smoother (zs -> scan), apply + pan + bus sum
     // L.eq1: the carries are scanned inside the zs / run kernels (the run kernel reads the zs kernel's states directly)
@@ -179,11 +136,11 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
     const float* sE_t = L.eq1 ? ws + L.zE_t : ws + L.sE_t;
     const float* sE_m = L.eq1 ? ws + L.zE_m : ws + L.sE_m;
     // a call that saves for backward also leaves the all-pole zero-state ends of the coefficient-gradient pass
-    float* zP_t = (save && fuse_allpole()) ? ws + L.zP_t : nullptr;
-    float* zP_m = (save && fuse_allpole()) ? ws + L.zP_m : nullptr;
+    float* zP_t = save ? ws + L.zP_t : nullptr;
+    float* zP_m = save ? ws + L.zP_m : nullptr;
     // round 5: the zero-state pass rides inside the run launch (tile aggregates exchanged as granules) wherever the run is a SCAN1 kernel
     // with that variant: the tracks' compressor-fused run and both master-bus runs
-    const bool zsin = L.eq1 && mfma_zs() && fuse_eq_zs();
+    const bool zsin = L.eq1;
     const ZsIn zi_t{ws + L.wzF_t, (gran_t*)(ws + L.eqg_f), L.eqg_nf, status};
     const ZsIn zi_m{ws + L.wzF_m, (gran_t*)(ws + L.eqg_f) + (int64_t)L.R * kMaxTiles1 * kStates, L.eqg_nf, status};
     // tracks: only while (almost) every tile of the launch is resident at once - with many rounds of workgroups (cfg #3: 32768 tiles, 8
@@ -193,7 +150,7 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
 #endif
     const bool zsin_t = zsin && t_comp && (int64_t)L.R * L.ntE <= MST_ZSIN_MAX_TILES;
     if (zsin_t) {}
-    else if (L.eq1 && mfma_zs()) launch_eq_zs_mfma(EQ_FWD, tracks, d->track_row_stride, ws + L.wzF_t, L.R, ws + L.zE_t, L.ncE_pad, n, L.R, stream, p1F_t, L.ntE, ws + L.aggF_t);
+    else if (L.eq1) launch_eq_zs_mfma(EQ_FWD, tracks, d->track_row_stride, ws + L.wzF_t, L.R, ws + L.zE_t, L.ncE_pad, n, L.R, stream, p1F_t, L.ntE, ws + L.aggF_t);
     else launch_cascade(EQ_FWD, false, tracks, d->track_row_stride, nullptr, 0, ws + L.rc_t, L.R, nullptr, ws + L.zE_t, L.ncE_pad, n, L.R, stream, p1F_t, L.ntE, ws + L.aggF_t);
     if (!L.eq1) launch_scan12(false, ws + L.zE_t, ws + L.sE_t, ws + L.powF_t, L.R, L.ncE, L.ncE_pad, L.KE, L.R, stream);
     if (t_comp)  // EQ run fused with the gain computer + per-block envelope aggregates
@@ -208,9 +165,7 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
                       busp, bus_stride, mixed_tracks, fx_on ? ws + L.fx_in : nullptr,
                       L.T, L.ncC_pad, d->track_lookahead, t_comp ? 1 : 0, n, aligned};
     launch_apply_tracks(ta, L.bs, stream);
-#ifdef MST_DEV_PROBE
-    if (g_probe_ev && g_probe_where == 1) (void)hipEventRecord(g_probe_ev, stream);
-#endif
+    MST_DEV_PROBE_AT(1, stream);
     // ---- fx bus: reverberate the send bus and add it to the stereo bus (reference mst/modules.py:275-284)
     if (fx_on) launch_fx_forward(fx_plan(L), fx->noise, fx->filters, (const float*)fx->tables, ws, busp, bus_stride, stream);
 
@@ -219,7 +174,7 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
         const bool apscan_m = L.apscan_fwd && zP_m && zP_t && p1F_m;
         const bool zsin_m = zsin && apscan_m;
         if (zsin_m) {}
-        else if (L.eq1 && mfma_zs()) launch_eq_zs_mfma(EQ_FWD, ws + L.bus, Ns, ws + L.wzF_m, 0, ws + L.zE_m, L.ncE_pad, n, 2 * L.bs, stream, p1F_m, L.ntE, ws + L.aggF_m);
+        else if (L.eq1) launch_eq_zs_mfma(EQ_FWD, ws + L.bus, Ns, ws + L.wzF_m, 0, ws + L.zE_m, L.ncE_pad, n, 2 * L.bs, stream, p1F_m, L.ntE, ws + L.aggF_m);
         else launch_cascade(EQ_FWD, false, ws + L.bus, Ns, nullptr, 0, ws + L.rc_m, 0, nullptr, ws + L.zE_m, L.ncE_pad, n, 2 * L.bs, stream, p1F_m, L.ntE, ws + L.aggF_m);
         if (!L.eq1) launch_scan12(false, ws + L.zE_m, ws + L.sE_m, ws + L.powF_m, 0, L.ncE, L.ncE_pad, L.KE, 2 * L.bs, stream);
         if (apscan_m)  // + the track rows' all-pole carry scan as extra workgroups of this (one wave per SIMD) launch
@@ -227,9 +182,8 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
                                      ws + L.zP_t, ws + L.sP_t, ws + L.powP_t, L.R * 12, L.ncE, L.apscan_sh, EQ_FWD, zsin_m ? &zi_m : nullptr);
         else
             launch_cascade(EQ_FWD, true, ws + L.bus, Ns, ws + L.v_m, Ns, ws + L.rc_m, 0, sE_m, nullptr, L.ncE_pad, n, 2 * L.bs, stream, p1F_m, L.ntE, ws + L.aggF_m, zP_m);
-        if (!fuse_comp_zs()) launch_comp_zs(2, ws + L.v_m, Ns, ws + L.rc_m, ws + L.zS_m, L.ncC_pad, n, L.bs, stream);
         MasterApplyArgs ma{ws + L.v_m, Ns, ws + L.rc_m, ws + L.zS_m, save ? ws + L.gs_m : nullptr, mix, n,
-                           L.ncC_pad, d->master_lookahead, 1, n, aligned, fuse_comp_zs() ? (gran_t*)(ws + L.gran_f) : nullptr, (int64_t)L.bs * L.nblkC, status};
+                           L.ncC_pad, d->master_lookahead, 1, n, aligned, (gran_t*)(ws + L.gran_f), (int64_t)L.bs * L.nblkC, status};
         launch_apply_master(ma, L.bs, stream);
     } else if (o_on) {
         MasterApplyArgs ma{ws + L.bus, Ns, ws + L.rc_m, nullptr, nullptr, mix, n, L.ncC_pad, 0, 0, n, aligned};
@@ -289,12 +243,8 @@ extern "C" int mst_console_forward_mirrored(const mst_console_desc* d, const flo
 }
 
 static void allpole_scan(const Layout& L, float* ws, int nsig_all, hipStream_t stream) {
-    if (L.apscan_fwd && fuse_allpole()) {
-        // nothing up front: the track rows' scans rode on the forward's master-bus run, the master rows' ride on the backward's adjoint run
-        (void)nsig_all;
-    } else {
-        launch_scan2(ws + L.zP_t, ws + L.sP_t, ws + L.powP_t, L.R, L.ncE, L.ncE_pad, L.KE, nsig_all, stream);
-    }
+    // L.apscan_fwd: nothing up front - the track rows' scans rode on the forward's master-bus run, the master rows' ride on the backward's adjoint run
+    if (!L.apscan_fwd) launch_scan2(ws + L.zP_t, ws + L.sP_t, ws + L.powP_t, L.R, L.ncE, L.ncE_pad, L.KE, nsig_all, stream);
 }
 
 extern "C" int mst_console_backward_prepare(const mst_console_desc* d, void* workspace, size_t workspace_bytes, void* stream_) {
@@ -303,9 +253,7 @@ extern "C" int mst_console_backward_prepare(const mst_console_desc* d, void* wor
     if (!workspace || workspace_bytes < (size_t)L.total * sizeof(float) || ((uintptr_t)workspace & 255)) return hipErrorInvalidValue;
     if (!(d->flags & MST_SAVE_FOR_BACKWARD) || (d->flags & MST_SPLIT_BATCH)) return hipErrorInvalidValue;
     float* ws = (float*)workspace;
-    const int64_t Ns = row_stride(L.N);
     const int nsig_all = L.R + ((d->flags & MST_USE_MASTER_BUS) ? 2 * L.bs : 0);
-    if (!fuse_allpole()) launch_allpole_zs(ws + L.u_t, Ns, ws + L.rc_t, L.R, ws + L.zP_t, L.ncE_pad, L.N, nsig_all, (hipStream_t)stream_);
     allpole_scan(L, ws, nsig_all, (hipStream_t)stream_);
     return (int)hipGetLastError();
 }
@@ -341,7 +289,6 @@ static int console_backward_impl(const mst_console_desc* d, const float* tracks,
     // launch covers the track rows and the master rows (signal rows [0,R) and [R,R+2bs) of the same arrays)
     const int nsig_all = L.R + (m_on ? 2 * L.bs : 0);
     if (!(d->flags & MST_BWD_PREPARED)) {  // else: mst_console_backward_prepare ran (on a side stream the caller has joined)
-        if (!fuse_allpole()) launch_allpole_zs(ws + L.u_t, Ns, ws + L.rc_t, L.R, ws + L.zP_t, L.ncE_pad, n, nsig_all, stream);
         allpole_scan(L, ws, nsig_all, stream);
     }
 
@@ -351,29 +298,27 @@ static int console_backward_impl(const mst_console_desc* d, const float* tracks,
     if (m_on) {
         CompBwdArgs ca{ws + L.v_m, Ns, ws + L.gs_m, ws + L.rc_m, nullptr, ws + L.zQ_m, ws + L.du_m, ws + L.cp_m,
                        grad_mix, n, nullptr, nullptr, 0, 1, L.ncC_pad, d->master_lookahead, 1, n, aligned};
-        if (fuse_comp_zs()) {
-            ca.gran = (gran_t*)(ws + L.gran_b) + 2 * (int64_t)L.R * L.nblkC;
-            ca.gran_near = (int64_t)L.bs * L.nblkC;
-            ca.status = status;
-        }
-        else launch_comp_bwd(true, false, ca, L.bs, stream);
+        // the adjoint smoother's block aggregates are exchanged inside the run launch (mst_common.h: granules)
+        ca.gran = (gran_t*)(ws + L.gran_b) + 2 * (int64_t)L.R * L.nblkC;
+        ca.gran_near = (int64_t)L.bs * L.nblkC;
+        ca.status = status;
         ca.s0 = ws + L.zQ_m;
         // coefficient-gradient sums of the two bus channels: in this launch (round 3), or - when the all-pole scans ride on other launches
         // (Layout::apscan_fwd) - as extra rows of the TRACKS' run launch below: the master launch is one lockstep round of lone
         // workgroups, where two more 64-sample walks per workgroup are pure latency (31 -> 18 us), the track launch absorbs them
-        const bool master_cg_later = MST_FUSE_COEFGRAD && L.apscan_fwd && fuse_allpole();
-        if (MST_FUSE_COEFGRAD && !master_cg_later) {
+        const bool master_cg_later = L.apscan_fwd;
+        if (!master_cg_later) {
             ca.ap_s0 = ws + L.sP_m;
             ca.ap_nc_pad = L.ncE_pad;
             ca.ep = ws + L.ep_m;
         }
-        launch_comp_bwd(true, true, ca, L.bs, stream);
+        launch_comp_bwd(true, ca, L.bs, stream);
         const float* p1A_m = L.eq1 ? ws + L.pow1A_m : nullptr;
         // round 5: the adjoint run carries its own zero-state pass when it is the SCAN1 kernel with the riders (ZsIn, mst_kernels.h)
-        const bool zsin_a = L.eq1 && mfma_zs() && fuse_eq_zs() && master_cg_later;
+        const bool zsin_a = L.eq1 && master_cg_later;
         const ZsIn zi_a{ws + L.wzA_m, (gran_t*)(ws + L.eqg_b), L.eqg_nb, status};
         if (zsin_a) {}
-        else if (L.eq1 && mfma_zs()) launch_eq_zs_mfma(EQ_ADJ, ws + L.du_m, Ns, ws + L.wzA_m, 0, ws + L.zA_m, L.ncE_pad, n, 2 * L.bs, stream, p1A_m, L.ntE, ws + L.aggA_m);
+        else if (L.eq1) launch_eq_zs_mfma(EQ_ADJ, ws + L.du_m, Ns, ws + L.wzA_m, 0, ws + L.zA_m, L.ncE_pad, n, 2 * L.bs, stream, p1A_m, L.ntE, ws + L.aggA_m);
         else launch_cascade(EQ_ADJ, false, ws + L.du_m, Ns, nullptr, 0, ws + L.rc_m, 0, nullptr, ws + L.zA_m, L.ncE_pad, n, 2 * L.bs, stream, p1A_m, L.ntE, ws + L.aggA_m);
         if (!L.eq1) launch_scan12(true, ws + L.zA_m, ws + L.sA_m, ws + L.powA_m, 0, L.ncE, L.ncE_pad, L.KE, 2 * L.bs, stream);
         if (master_cg_later)  // + the master rows' own all-pole carry scans as extra workgroups of this (one wave per SIMD) launch
@@ -387,7 +332,7 @@ static int console_backward_impl(const mst_console_desc* d, const float* tracks,
     } else if (o_on) {
         CompBwdArgs ca{ws + L.bus, Ns, nullptr, ws + L.rc_m, nullptr, nullptr, ws + L.dbus, ws + L.cp_m,
                        grad_mix, n, nullptr, nullptr, 0, 1, L.ncC_pad, 0, 0, n, aligned};
-        launch_comp_bwd(true, true, ca, L.bs, stream);
+        launch_comp_bwd(true, ca, L.bs, stream);
         gbus = ws + L.dbus;
         gbus_stride = Ns;
     } else {
@@ -403,34 +348,27 @@ static int console_backward_impl(const mst_console_desc* d, const float* tracks,
                        gbus, gbus_stride, grad_mixed_tracks, fx_on ? ws + L.fx_din : nullptr, Ns, L.T, L.ncC_pad, d->track_lookahead,
                        t_comp ? 1 : 0, n, aligned};
         if (t_comp) {
-            if (fuse_comp_zs()) {
-                ca.gran = (gran_t*)(ws + L.gran_b);
-                ca.gran_near = (int64_t)L.R * L.nblkC;
-                ca.status = status;
-            }
-            else launch_comp_bwd(false, false, ca, L.R, stream);
+            ca.gran = (gran_t*)(ws + L.gran_b);
+            ca.gran_near = (int64_t)L.R * L.nblkC;
+            ca.status = status;
             ca.s0 = ws + L.zQ_t;
         }
-        if (MST_FUSE_COEFGRAD) {
-            // the run pass forms the tracks' coefficient-gradient sums from the du and u it holds in registers: du crosses HBM only
-            // when the EQ adjoint below needs it (grad_tracks), u is not read a second time
-            ca.ap_s0 = ws + L.sP_t;
-            ca.ap_nc_pad = L.ncE_pad;
-            ca.ep = ws + L.ep_t;
-            if (!grad_tracks) ca.du = nullptr;
-            if (m_on && L.apscan_fwd && fuse_allpole()) {  // the master channels' coefficient-gradient walks ride here (see above)
-                ca.cg2_u = ws + L.v_m;
-                ca.cg2_du = ws + L.du_m;
-                ca.cg2_rc = ws + L.rc_m;
-                ca.cg2_rows = 2 * L.bs;
-            }
+        // the run pass forms the tracks' coefficient-gradient sums from the du and u it holds in registers: du crosses HBM only
+        // when the EQ adjoint below needs it (grad_tracks), u is not read a second time
+        ca.ap_s0 = ws + L.sP_t;
+        ca.ap_nc_pad = L.ncE_pad;
+        ca.ep = ws + L.ep_t;
+        if (!grad_tracks) ca.du = nullptr;
+        if (m_on && L.apscan_fwd) {  // the master channels' coefficient-gradient walks ride here (see above)
+            ca.cg2_u = ws + L.v_m;
+            ca.cg2_du = ws + L.du_m;
+            ca.cg2_rc = ws + L.rc_m;
+            ca.cg2_rows = 2 * L.bs;
         }
-        launch_comp_bwd(false, true, ca, L.R, stream);
-        // without the fusion: one k_coefgrad launch for the track rows and the master rows (which follow the tracks in the same arrays)
-        if (!MST_FUSE_COEFGRAD) launch_coefgrad(ws + L.u_t, Ns, ws + L.du_t, Ns, ws + L.rc_t, L.R, ws + L.sP_t, L.ncE_pad, ws + L.ep_t, n, nsig_all, stream);
+        launch_comp_bwd(false, ca, L.R, stream);
         if (grad_tracks) {
             const float* p1A_t = L.eq1 ? ws + L.pow1A_t : nullptr;
-            if (L.eq1 && mfma_zs()) launch_eq_zs_mfma(EQ_ADJ, ws + L.du_t, Ns, ws + L.wzA_t, L.R, ws + L.zA_t, L.ncE_pad, n, L.R, stream, p1A_t, L.ntE, ws + L.aggA_t);
+            if (L.eq1) launch_eq_zs_mfma(EQ_ADJ, ws + L.du_t, Ns, ws + L.wzA_t, L.R, ws + L.zA_t, L.ncE_pad, n, L.R, stream, p1A_t, L.ntE, ws + L.aggA_t);
             else launch_cascade(EQ_ADJ, false, ws + L.du_t, Ns, nullptr, 0, ws + L.rc_t, L.R, nullptr, ws + L.zA_t, L.ncE_pad, n, L.R, stream, p1A_t, L.ntE, ws + L.aggA_t);
             if (!L.eq1) launch_scan12(true, ws + L.zA_t, ws + L.sA_t, ws + L.powA_t, L.R, L.ncE, L.ncE_pad, L.KE, L.R, stream);
             launch_cascade(EQ_ADJ, true, ws + L.du_t, Ns, grad_tracks, n, ws + L.rc_t, L.R, L.eq1 ? ws + L.zA_t : ws + L.sA_t, nullptr, L.ncE_pad,

@@ -17,7 +17,8 @@
 //   The adjoint (reverse-time) cascade uses the same skeleton with time reversed.
 //   Coefficient gradients use the forward-only identity  dL/db_kj = <g, S^j (1/B_k) u>,
 //   dL/da_kj = -<g, S^j (1/A_k) u>  (u = EQ output, g = its cotangent): twelve independent 2-state
-//   all-pole recurrences on u, same zs / scan / run structure (k_allpole_zs, k_coefgrad).
+//   all-pole recurrences on u, same zs / scan / run structure (the zs part rides on the forward run: FUSE_AP; the walk
+//   itself happens in the compressor backward, mst_comp.hip: coefgrad_fused).
 #include "mst_kernels.h"
 #include "mst_mat.h"
 #include "mst_compdev.h"
@@ -76,37 +77,9 @@ __device__ __forceinline__ void slab_store(const float* __restrict__ tile, float
     }
 }
 
-// Build-time variants of the staging pipeline (A/B on the GPU; defaults are the measured best):
-//   MST_EQ_PREFETCH  1: the next slab's global loads are issued before the current slab is filtered
-//                    0: each slab is fetched when it is needed (fewer live registers)
-//   MST_EQ_SCHEDBAR  1: a scheduling barrier closes every slab iteration (single-wave workgroups have no
-//                       real barrier, and the compiler otherwise hoists the staging of ALL slabs above the math)
-#ifndef MST_EQ_PREFETCH
-#define MST_EQ_PREFETCH 1
-#endif
-#ifndef MST_EQ_SCHEDBAR
-#define MST_EQ_SCHEDBAR 0
-#endif
-template <bool FAST>
-__device__ __forceinline__ void slab_first(SlabRegs& r, const float* __restrict__ row, int64_t tile_base, int j, int64_t n, int tid) {
-    if (MST_EQ_PREFETCH) slab_fetch<FAST>(r, row, tile_base, j, n, tid);
-}
-template <bool FAST>
-__device__ __forceinline__ void slab_enter(SlabRegs& r, const float* __restrict__ row, int64_t tile_base, int j, int64_t n, int tid) {
-    if (!MST_EQ_PREFETCH) slab_fetch<FAST>(r, row, tile_base, j, n, tid);
-}
-template <bool FAST>
-__device__ __forceinline__ void slab_next(SlabRegs& r, const float* __restrict__ row, int64_t tile_base, int j, bool valid, int64_t n, int tid) {
-    if (MST_EQ_PREFETCH && valid) slab_fetch<FAST>(r, row, tile_base, j, n, tid);
-}
 // whole-workgroup decision: the tile lies inside the row and the row base allows 16-byte accesses
 __device__ __forceinline__ bool tile_fast(const float* row, int64_t tile_base, int64_t n) {
     return tile_base + kTile <= n && !((uintptr_t)row & 15);
-}
-__device__ __forceinline__ void slab_fence() {
-#if MST_EQ_SCHEDBAR
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 
 // ---- zero-state chunk end states of one tile on the matrix pipe (the arithmetic of k_eq_zs_mfma below, which explains it) ----------
@@ -158,9 +131,9 @@ __device__ __forceinline__ void zs_inline(const float* __restrict__ row, int64_t
 // MODE_RUN = true : true pass from s0[sig][12][nc_pad], writes out
 // FUSE_GC (forward run of mono rows only): the compressor's static curve is evaluated on the fresh EQ
 // output and the zero-state envelope end value of every 2048-sample compressor block (= 32 lanes) is
-// written to zs_comp[sig][block] - this replaces the separate k_comp_zs pass over the EQ output.
+// written to zs_comp[sig][block] - no separate pass over the EQ output.
 // FUSE_AP (forward run, when the call saves for backward): the all-pole bank of the coefficient-gradient pass
-// (k_allpole_zs) advances on the fresh EQ output too and its zero-state chunk end states go to zp - the backward then
+// advances on the fresh EQ output too and its zero-state chunk end states go to zp - the backward then
 // starts at the all-pole carry scan, one pass over u less.
 template <int DIR, bool MODE_RUN, bool FUSE_GC, bool SCAN1, bool FAST, bool FUSE_AP, bool ZSIN = false>
 __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64_t in_stride,
@@ -205,7 +178,7 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
         for (int i = 0; i < kStates; ++i) st[i] = dpp_get<(DIR == EQ_ADJ) ? 0x130 : 0x138>(st[i]);
     }
     SlabRegs pre;
-    slab_first<FAST>(pre, inrow, tile_base, order(0), n, tid);  // first slab in flight while constants load
+    slab_fetch<FAST>(pre, inrow, tile_base, order(0), n, tid);  // first slab in flight while constants load
 
     const float* coef = rc + (int64_t)filter_row(sig, split) * RC_STRIDE + RC_SOS;
     float c[5 * kSections];
@@ -221,10 +194,7 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
 #pragma unroll
             for (int i = 0; i < kStates; ++i) st[i] = pos > 0 ? s0[((int64_t)sig * kStates + i) * nc_pad + nb] : 0.0f;
         }
-#ifndef MST_DBG_NOSCAN
-#define MST_DBG_NOSCAN 0  // timing diagnostics only: 1 skips the in-wave carry scans (wrong results)
-#endif
-        if (wt > 0 && !MST_DBG_NOSCAN) {
+        if (wt > 0) {
             float zz[kStates];  // lane q looks at the tile at recurrence position q
             if (ZSIN) {
                 gran_read_vec<kStates>(zi.gran + ((int64_t)sig * kMaxTiles1 + tid) * kStates, zi.gran_near, zz, tid < wt, zi.status);
@@ -242,12 +212,10 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
             }
             wave_lds_sync();
         }
-        if (!MST_DBG_NOSCAN) {
-            tab_stash(tlo, tile, tid);
-            wave_lds_sync();
-            wave_scan_tri<DIR == EQ_ADJ>(st, tile, pos);
-            wave_lds_sync();  // the slab image overwrites the table next
-        }
+        tab_stash(tlo, tile, tid);
+        wave_lds_sync();
+        wave_scan_tri<DIR == EQ_ADJ>(st, tile, pos);
+        wave_lds_sync();  // the slab image overwrites the table next
     } else {
 #pragma unroll
         for (int i = 0; i < kStates; ++i)
@@ -257,7 +225,7 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
     CompK ck{};
     float zacc = 0.0f;
     if (FUSE_GC) ck = load_comp(rc + (int64_t)filter_row(sig, split) * RC_STRIDE);
-    // the all-pole bank of k_coefgrad, zero state: 1/A_k on (wa1, wa2), b0/B_k on (wb1, wb2); a1, a2 are c[5s+3], c[5s+4]
+    // the all-pole bank of the coefficient-gradient pass, zero state: 1/A_k on (wa1, wa2), b0/B_k on (wb1, wb2); a1, a2 are c[5s+3], c[5s+4]
     // held as pairs (1/A_k side, b0/B_k side): the two recurrences of a section are one packed multiply-add each (v_pk_fma_f32)
     f2 nk1[kSections], nk2[kSections], w1[kSections], w2[kSections];
     if (FUSE_AP) {
@@ -274,7 +242,8 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
                          // multiply-adds on (b1, b2) x + (s2, 0), bit-identical to the scalar form: 47.4 us against 47.0 (the pair
                          // assembly costs the instruction it saves).  The variant s1' = (b1 x - a1 y) + s2 measured 44.7 against 46.5
                          // but moved the most ill-conditioned golden fixture from 2.13x to 2.57x the fp32 reference's distance from
-                         // float64 - not taken
+                         // float64 - not taken.  The switch stays in the tree: without the (dead) packed body the three register-capped
+                         // forward-run kernels come out with three register copies in another order
 #endif
     f2 sp[kSections], cb[kSections], can[kSections];
     if (DIR == EQ_FWD && MST_EQ_PACKED) {
@@ -288,7 +257,7 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
     auto step_fwd = [&](float x) {
         if (!MST_EQ_PACKED) return cascade_step<float>(x, c, st);
 #pragma unroll
-        for (int s = 0; s < MST_DBG_SECTIONS; ++s) {
+        for (int s = 0; s < kSections; ++s) {
             const float y = fmaf(c[5 * s], x, sp[s].x);
             // same roundings as biquad_step: (n1, t) = (b1, b2) x + (s2, 0);  (s1', s2') = -(a1, a2) y + (n1, t)
             sp[s] = f2_fma(can[s], f2{y, y}, f2_fma(cb[s], f2{x, x}, f2{sp[s].y, 0.0f}));
@@ -298,10 +267,9 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
     };
     for (int jj = 0; jj < kNSlab; ++jj) {
         const int j = order(jj);
-        slab_enter<FAST>(pre, inrow, tile_base, j, n, tid);
         slab_stash(pre, tile, tid);
         wave_lds_sync();
-        slab_next<FAST>(pre, inrow, tile_base, order(jj + 1 < kNSlab ? jj + 1 : jj), jj + 1 < kNSlab, n, tid);
+        if (jj + 1 < kNSlab) slab_fetch<FAST>(pre, inrow, tile_base, order(jj + 1), n, tid);  // the next slab's loads fly behind this slab's filtering
         if (DIR == EQ_FWD) {
 #pragma unroll
             for (int i4 = 0; i4 < kSlab; i4 += 4) {
@@ -347,7 +315,6 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
             slab_store<FAST>(tile, outrow, tile_base, j, n, tid);
             wave_lds_sync();  // the image is read by other lanes' stores before the next stash overwrites it
         }
-        slab_fence();
     }
     if (DIR == EQ_FWD && MST_EQ_PACKED) {
 #pragma unroll
@@ -359,7 +326,7 @@ __device__ __forceinline__ void cascade_body(const float* __restrict__ in, int64
     if (!MODE_RUN) {
 #pragma unroll
         for (int i = 0; i < kStates; ++i) z[((int64_t)sig * kStates + i) * nc_pad + chunk] = st[i];
-        if (SCAN1 && !MST_DBG_NOSCAN) {  // tile aggregate = the last position of the scan over the tile's chunk end states
+        if (SCAN1) {  // tile aggregate = the last position of the scan over the tile's chunk end states
             tab_stash(tlo, tile, tid);  // the slab buffer is free now
             wave_lds_sync();
             wave_scan_tri<DIR == EQ_ADJ>(st, tile, pos);
@@ -493,7 +460,7 @@ void launch_eq_zs_mfma(int dir, const float* in, int64_t in_stride, const float*
 //   pass 1  fold the lane's 64 chunks from zero:  s <- P s + z_c                      (P = A_f^64, table entry 0)
 //   scan    inclusive Hillis-Steele over the lanes with P^(64 2^j) = table entry 1 + sh + j, 64 = KE 2^sh (the tables k_prep makes
 //           for k_scan: (P^KE)^(2^j)), exclusive shift -> the state entering the lane's first chunk
-//   pass 2  replay from there, emitting the state ENTERING every chunk in the layout k_coefgrad / coefgrad_fused read.
+//   pass 2  replay from there, emitting the state ENTERING every chunk in the layout coefgrad_fused (mst_comp.hip) reads.
 // Same recurrences, same fp32 products as k_scan; the association of the lane-level scan differs (64 x 64 instead of 512 x 8).
 template <bool FAST>
 __device__ __forceinline__ void allpole_scan_tile(const float* __restrict__ z0, float* __restrict__ o0, const float* __restrict__ tab, int nc,
@@ -585,12 +552,9 @@ __global__ __launch_bounds__(kEqWG) void k_master_run_apscan(const float* __rest
                                                            int nc_pad, int64_t n, const float* __restrict__ pw1, int ntiles,
                                                            float* __restrict__ agg, float* __restrict__ zp, int nsig, ApScanArgs sc, ZsIn zi) {
     __shared__ __attribute__((aligned(16))) float tile[2 * kEqWG * kLdw > kTriFloats ? 2 * kEqWG * kLdw : kTriFloats];
-#ifndef MST_DBG_APSCAN
-#define MST_DBG_APSCAN 0  // timing diagnostics only (wrong results): 1 = the scan role returns at once, 2 = the cascade role does
-#endif
     if ((int)blockIdx.y >= nsig) {
         const int job = ((int)blockIdx.y - nsig) * gridDim.x + blockIdx.x;
-        if (job >= sc.jobs || MST_DBG_APSCAN == 1) return;
+        if (job >= sc.jobs) return;
         const float* z0 = sc.z + (int64_t)job * 2 * sc.nc_pad;
         float* o0 = sc.s0 + (int64_t)job * 2 * sc.nc_pad;
         const int trow = sc.stereo ? ((job / 12) >> 1) * 12 + job % 12 : job;
@@ -599,7 +563,6 @@ __global__ __launch_bounds__(kEqWG) void k_master_run_apscan(const float* __rest
         else allpole_scan_tile<false>(z0, o0, tab, sc.nc, sc.nc_pad, sc.sh, tile, tile + kEqWG * kLdw, threadIdx.x);
         return;
     }
-    if (MST_DBG_APSCAN == 2) return;
     int sig = blockIdx.y, bx = blockIdx.x;
     if (ZSIN) {  // the cascade workgroups (ids 0 .. ntiles nsig - 1, ahead of the scan jobs) exchange tile aggregates: see k_cascade_zsin
         int step;
@@ -628,193 +591,6 @@ void launch_master_run_apscan(const float* in, int64_t in_stride, float* out, in
         else MST_LAUNCH_MRA(EQ_ADJ, false);
     }
 #undef MST_LAUNCH_MRA
-}
-
-// ---- all-pole bank for the coefficient gradients ------------------------------------------------
-// filter f = 2k : w = u - a1 w1 - a2 w2 (1/A_k);  f = 2k+1 : w = u - (b1/b0) w1 - (b2/b0) w2 (b0/B_k: the 1/b0 of 1/B_k is
-// applied once, to the finished inner products - one multiply per sample and section less in all three kernels)
-struct ApCoef {
-    float a1[kSections], a2[kSections], ib0[kSections], c1[kSections], c2[kSections];
-};
-__device__ __forceinline__ void load_ap(const float* rcrow, ApCoef& k) {  // rcrow = the filter row's constants
-#pragma unroll
-    for (int s = 0; s < kSections; ++s) {
-        k.a1[s] = rcrow[RC_SOS + 5 * s + 3];
-        k.a2[s] = rcrow[RC_SOS + 5 * s + 4];
-        k.c1[s] = rcrow[RC_AP + 3 * s];
-        k.c2[s] = rcrow[RC_AP + 3 * s + 1];
-        k.ib0[s] = rcrow[RC_AP + 3 * s + 2];
-    }
-}
-
-// zero-state end states of the 12 all-pole filters per lane chunk: z[sig][24][nc_pad]
-template <bool FAST>
-__device__ __forceinline__ void allpole_zs_body(const float* __restrict__ u, int64_t u_stride,
-                                                const float* __restrict__ rc, int split, float* __restrict__ z,
-                                                int nc_pad, int64_t n, float* __restrict__ tile) {
-    const int tid = threadIdx.x, sig = blockIdx.y;
-    const int64_t tile_base = (int64_t)blockIdx.x * kEqWG * kEqChunk;
-    const int chunk = blockIdx.x * kEqWG + tid;
-    ApCoef k;
-    load_ap(rc + (int64_t)filter_row(sig, split) * RC_STRIDE, k);
-    float wa1[kSections], wa2[kSections], wb1[kSections], wb2[kSections];
-#pragma unroll
-    for (int s = 0; s < kSections; ++s) wa1[s] = wa2[s] = wb1[s] = wb2[s] = 0.0f;
-    const float* urow = u + (int64_t)sig * u_stride;
-    float* mine = &tile[tid * kLdw];
-    SlabRegs pre;
-    slab_first<FAST>(pre, urow, tile_base, 0, n, tid);
-    for (int j = 0; j < kNSlab; ++j) {
-        slab_enter<FAST>(pre, urow, tile_base, j, n, tid);
-        slab_stash(pre, tile, tid);
-        wave_lds_sync();
-        slab_next<FAST>(pre, urow, tile_base, j + 1, j + 1 < kNSlab, n, tid);
-#pragma unroll 4
-        for (int i = 0; i < kSlab; ++i) {
-            const float x = mine[i];
-#pragma unroll
-            for (int s = 0; s < kSections; ++s) {
-                const float wa = fmaf(-k.a2[s], wa2[s], fmaf(-k.a1[s], wa1[s], x));
-                wa2[s] = wa1[s];
-                wa1[s] = wa;
-                const float wb = fmaf(-k.c2[s], wb2[s], fmaf(-k.c1[s], wb1[s], x));
-                wb2[s] = wb1[s];
-                wb1[s] = wb;
-            }
-        }
-        wave_lds_sync();
-        slab_fence();
-    }
-#pragma unroll
-    for (int s = 0; s < kSections; ++s) {
-        const int64_t base = ((int64_t)sig * 24 + 4 * s) * nc_pad + chunk;
-        z[base] = wa1[s];
-        z[base + nc_pad] = wa2[s];
-        z[base + 2 * (int64_t)nc_pad] = wb1[s];
-        z[base + 3 * (int64_t)nc_pad] = wb2[s];
-    }
-}
-
-__global__ __launch_bounds__(kEqWG) void k_allpole_zs(const float* __restrict__ u, int64_t u_stride,
-                                                    const float* __restrict__ rc, int split, float* __restrict__ z,
-                                                    int nc_pad, int64_t n) {
-    __shared__ __attribute__((aligned(16))) float tile[kEqWG * kLdw];
-    if (tile_fast(u + (int64_t)blockIdx.y * u_stride, (int64_t)blockIdx.x * kTile, n)) allpole_zs_body<true>(u, u_stride, rc, split, z, nc_pad, n, tile);
-    else allpole_zs_body<false>(u, u_stride, rc, split, z, nc_pad, n, tile);
-}
-
-// coefficient-gradient partial sums: part[sig][block][30] = {db0 db1 db2 da1 da2} x 6 sections
-// TWO waves per tile: both walk the same 64 chunks, wave h owns sections 3h .. 3h+2 (the bank's sections are independent:
-// every one filters the same u and is correlated with the same g).  Wave 0 stages the u slabs, wave 1 the g slabs, each lane
-// reads both images.  One wave per tile needed 144 registers (3 waves per SIMD, 5120 workgroups = 1.67 rounds at cfg #2);
-// half the sections per wave halve the arithmetic per wave and the register count with it.
-constexpr int kCgSec = kSections / 2;
-template <bool FAST>
-__device__ __forceinline__ void coefgrad_body(const float* __restrict__ u, int64_t u_stride,
-                                              const float* __restrict__ g, int64_t g_stride,
-                                              const float* __restrict__ rc, int split,
-                                              const float* __restrict__ s0, int nc_pad,
-                                              float* __restrict__ part, int64_t n, float* __restrict__ tile_u,
-                                              float* __restrict__ tile_g, float (*red)[EP_COUNT / 2]) {
-    const int tid = threadIdx.x & 63, half = threadIdx.x >> 6, sig = blockIdx.y;
-    const int64_t tile_base = (int64_t)blockIdx.x * kEqWG * kEqChunk;
-    const int chunk = blockIdx.x * kEqWG + tid;
-    // Per sample and section: 1/A_k and b0/B_k advance (2 FMAs each) and their five inner products with the cotangent
-    // accumulate (5 FMAs) - 9 plain FMAs.  (Round 1 packed the filter pair into v_pk_fma_f32: 6 packed operations, which on
-    // gfx950 issue at HALF rate - 12 issue slots where these take 9, and a lane of one product was idle.)
-    const float* rcrow = rc + (int64_t)filter_row(sig, split) * RC_STRIDE;
-    float ka1[kCgSec], ka2[kCgSec], kc1[kCgSec], kc2[kCgSec], kib0[kCgSec];
-    float wa1[kCgSec], wa2[kCgSec], wb1[kCgSec], wb2[kCgSec];
-    float db0[kCgSec], db1[kCgSec], db2[kCgSec], da1[kCgSec], da2[kCgSec];
-#pragma unroll
-    for (int j = 0; j < kCgSec; ++j) {
-        const int s = kCgSec * half + j;
-        ka1[j] = rcrow[RC_SOS + 5 * s + 3];
-        ka2[j] = rcrow[RC_SOS + 5 * s + 4];
-        kc1[j] = rcrow[RC_AP + 3 * s];
-        kc2[j] = rcrow[RC_AP + 3 * s + 1];
-        kib0[j] = rcrow[RC_AP + 3 * s + 2];
-        const int64_t base = ((int64_t)sig * 24 + 4 * s) * nc_pad + chunk;
-        wa1[j] = s0[base];
-        wa2[j] = s0[base + nc_pad];
-        wb1[j] = s0[base + 2 * (int64_t)nc_pad];
-        wb2[j] = s0[base + 3 * (int64_t)nc_pad];
-        db0[j] = db1[j] = db2[j] = da1[j] = da2[j] = 0.0f;
-    }
-    const float* srow = half == 0 ? u + (int64_t)sig * u_stride : g + (int64_t)sig * g_stride;  // the stream this wave stages
-    float* simg = half == 0 ? tile_u : tile_g;
-    float* mu = &tile_u[tid * kLdw];
-    float* mg = &tile_g[tid * kLdw];
-    SlabRegs pre;
-    slab_first<FAST>(pre, srow, tile_base, 0, n, tid);
-    for (int j = 0; j < kNSlab; ++j) {
-        slab_enter<FAST>(pre, srow, tile_base, j, n, tid);
-        slab_stash(pre, simg, tid);
-        lds_barrier();
-        slab_next<FAST>(pre, srow, tile_base, j + 1, j + 1 < kNSlab, n, tid);
-#pragma unroll 1
-        for (int i4 = 0; i4 < kSlab; i4 += 4) {
-            const float4 xv = *reinterpret_cast<const float4*>(&mu[i4]);
-            const float4 gv = *reinterpret_cast<const float4*>(&mg[i4]);
-            const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float x = xs[t], gp = gs[t], gm = -gs[t];
-#pragma unroll
-                for (int q = 0; q < kCgSec; ++q) {
-                    const float wa = fmaf(-ka2[q], wa2[q], fmaf(-ka1[q], wa1[q], x));
-                    const float wb = fmaf(-kc2[q], wb2[q], fmaf(-kc1[q], wb1[q], x));
-                    db0[q] = fmaf(gp, wb, db0[q]);
-                    db1[q] = fmaf(gp, wb1[q], db1[q]);
-                    db2[q] = fmaf(gp, wb2[q], db2[q]);
-                    da1[q] = fmaf(gm, wa1[q], da1[q]);
-                    da2[q] = fmaf(gm, wa2[q], da2[q]);
-                    wa2[q] = wa1[q];
-                    wa1[q] = wa;
-                    wb2[q] = wb1[q];
-                    wb1[q] = wb;
-                }
-            }
-        }
-        lds_barrier();
-        slab_fence();
-    }
-    float acc[EP_COUNT / 2];
-#pragma unroll
-    for (int q = 0; q < kCgSec; ++q) {
-        acc[5 * q + 0] = db0[q] * kib0[q];
-        acc[5 * q + 1] = db1[q] * kib0[q];
-        acc[5 * q + 2] = db2[q] * kib0[q];
-        acc[5 * q + 3] = da1[q];
-        acc[5 * q + 4] = da2[q];
-    }
-    // deterministic reduction: one DPP sum per value, lane 0 of each wave parks its 15
-#pragma unroll
-    for (int i = 0; i < EP_COUNT / 2; ++i) {
-        const float v = wave_sum(acc[i]);
-        if (tid == 0) red[half][i] = v;
-    }
-    lds_barrier();
-    if (threadIdx.x < EP_COUNT)
-        part[((int64_t)sig * gridDim.x + blockIdx.x) * EP_COUNT + threadIdx.x] = red[threadIdx.x / (EP_COUNT / 2)][threadIdx.x % (EP_COUNT / 2)];
-}
-
-#ifndef MST_COEFGRAD_W
-#define MST_COEFGRAD_W 1  // min waves per SIMD asked of k_coefgrad (A/B switch)
-#endif
-__global__ __launch_bounds__(2 * kEqWG, MST_COEFGRAD_W) void k_coefgrad(const float* __restrict__ u, int64_t u_stride,
-                                                  const float* __restrict__ g, int64_t g_stride,
-                                                  const float* __restrict__ rc, int split,
-                                                  const float* __restrict__ s0, int nc_pad,
-                                                  float* __restrict__ part, int64_t n) {
-    __shared__ __attribute__((aligned(16))) float tile_u[kEqWG * kLdw];
-    __shared__ __attribute__((aligned(16))) float tile_g[kEqWG * kLdw];
-    __shared__ float red[2][EP_COUNT / 2];
-    const int64_t tile_base = (int64_t)blockIdx.x * kTile;
-    if (tile_fast(u + (int64_t)blockIdx.y * u_stride, tile_base, n) && !((uintptr_t)(g + (int64_t)blockIdx.y * g_stride) & 15))
-        coefgrad_body<true>(u, u_stride, g, g_stride, rc, split, s0, nc_pad, part, n, tile_u, tile_g, red);
-    else
-        coefgrad_body<false>(u, u_stride, g, g_stride, rc, split, s0, nc_pad, part, n, tile_u, tile_g, red);
 }
 
 // ---- host-side launch helpers (called from mst_console.hip) --------------------------------------
@@ -876,18 +652,6 @@ void launch_cascade_run_gc(const float* in, int64_t in_stride, float* out, int64
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, true, false>), grid, block, 0, stream, in, in_stride, out, out_stride,
                            rc, split, s0, (float*)nullptr, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, agg, (float*)nullptr);
-}
-
-void launch_allpole_zs(const float* u, int64_t u_stride, const float* rc, int split, float* z, int nc_pad, int64_t n,
-                       int nsig, hipStream_t stream) {
-    dim3 grid(nc_pad / kEqWG, nsig), block(kEqWG);
-    hipLaunchKernelGGL(k_allpole_zs, grid, block, 0, stream, u, u_stride, rc, split, z, nc_pad, n);
-}
-
-void launch_coefgrad(const float* u, int64_t u_stride, const float* g, int64_t g_stride, const float* rc, int split,
-                     const float* s0, int nc_pad, float* part, int64_t n, int nsig, hipStream_t stream) {
-    dim3 grid(nc_pad / kEqWG, nsig), block(2 * kEqWG);
-    hipLaunchKernelGGL(k_coefgrad, grid, block, 0, stream, u, u_stride, g, g_stride, rc, split, s0, nc_pad, part, n);
 }
 
 }  // namespace mst

@@ -24,41 +24,14 @@
 //                  (loads are 3x cheaper than stores on this LDS, MI355X_MICROARCH.md)
 #pragma once
 #include "mst_common.h"
-#ifndef MST_FFT2_SWIZZLE
-#define MST_FFT2_SWIZZLE 0
-#endif
-#ifndef MST_FFT2_PAD64
-#define MST_FFT2_PAD64 0  // A/B switch: 1 = the load-conflict-free images described at FftShape::slot1 (round 5).  Measured and NOT taken: the
-                          // bench kernels are unchanged (k_stft3_fwd 72.4 vs 72.4 us, k_stft2_bwd_512_2048 71.7 vs 71.7) and the engine alone
-                          // (tools/ubench/wf512.hip, 4 / 8 waves per SIMD) runs 846 / 776 cycles per transform against 823 / 743 - the two-way
-                          // load conflicts the counter reports are not what these kernels wait for
-#endif
 
 namespace mst {
 
-// A/B switch MST_FFT_PK: complex values as float pairs on the packed fp32 instructions (a complex add = one v_pk_add_f32, a product =
-// v_pk_mul_f32 + v_pk_fma_f32 with the swapped, half-negated operand on the op_sel / neg modifiers).  Measured and NOT taken: the
-// instruction count falls 3-10 % only (the pair assembly costs a v_mov for most of what it saves) while the even-aligned pairs raise the
-// register need - 8192 forward spills 49 registers at its 128 cap (33.6 -> 64.1 us), 512 / 2048 backward leave the four-waves-per-SIMD
-// budget (37.2 -> 47.5, 42.7 -> 51.7 us), and even the spill-free 512 forward is slower (20.9 -> 22.4 us).
-#ifndef MST_FFT_PK
-#define MST_FFT_PK 0
-#endif
-#if MST_FFT_PK && defined(__clang__)
-__device__ __forceinline__ f2 c2v(float2 a) { return f2{a.x, a.y}; }
-__device__ __forceinline__ float2 v2c(f2 a) { return make_float2(a.x, a.y); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return v2c(c2v(a) + c2v(b)); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return v2c(c2v(a) - c2v(b)); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return v2c(f2_fma(f2{a.y, a.y}, f2{-b.y, b.x}, f2{a.x, a.x} * c2v(b)));
-}
-__device__ __forceinline__ float2 cscale(float c, float2 a) { return v2c(f2{c, c} * c2v(a)); }
-#else
+// complex values on scalar fp32 instructions (as float pairs on the packed ones they measured slower: DESIGN 10.4.1)
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cscale(float c, float2 a) { return make_float2(c * a.x, c * a.y); }
-#endif
 __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
 __device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // a * (-i)
 __device__ __forceinline__ float2 mul_pi(float2 a) { return make_float2(-a.y, a.x); }  // a * (+i)
@@ -109,8 +82,7 @@ struct FftShape {
     // (offsets fold into the ds instructions) and wins for the small transforms; the XOR swizzle makes the loads conflict-free
     // too and needs no padding - it wins for the 4096-point sequences (8192 forward 40.5 -> 37.3 us, backward 77 -> 72 us) and
     // loses below (2048 forward 27.9 -> 32.7 us, 512 backward 48.9 -> 58.4 us)
-    static constexpr bool SWZ = MST_FFT2_SWIZZLE ? true : (M >= 4096);
-    static constexpr bool PAD64 = MST_FFT2_PAD64;
+    static constexpr bool SWZ = M >= 4096;
     static constexpr int SLOTS = SWZ ? M : M + M / 8;
     static constexpr int TWSCALE = N / M;          // W_M^e = W_N^(TWSCALE e)
     static_assert(M / 8 == LG, "one radix-8 butterfly per lane and sequence in every pass but the last");
@@ -118,82 +90,49 @@ struct FftShape {
     // of rows swap halves with row bit 3, so that every access pattern of the passes (a column of 16 rows, 8 + 8 lanes into
     // rows 8 apart, 16 / 32 consecutive elements) touches each bank once
     __device__ static __forceinline__ constexpr int slot(int i) {
-        return SWZ ? (i ^ (((i >> 4) & 7) | ((i >> 3) & 8))) : (PAD64 ? i + ((i >> 6) << 3) : i + (i >> 3));
+        return SWZ ? (i ^ (((i >> 4) & 7) | ((i >> 3) & 8))) : i + (i >> 3);
     }
-    // Round 5 (PAD64, the padded maps only): the pad sits behind every 64 elements (8 slots) instead of behind every 8 (1 slot).  With
-    // one pad slot per 8 elements a run of 32 lane-consecutive elements - every LOAD of the passes, every bin read of the epilogues -
-    // spans 35-36 slots = more than the 64 banks a ds_read_b64 group covers: three lanes wrap onto busy banks and the group takes two
-    // LDS cycles instead of one (SQ_LDS_BANK_CONFLICT 35-40 % of the LDS cycles of the 512- / 2048-point kernels, rounds 2-4).  Runs of 32
-    // never cross a multiple of 64, so now they are 32 consecutive slots.  The stores stay conflict-free: Ns = 8 stores put eight
-    // consecutive lanes on eight consecutive slots and the next eight lanes 72 slots = 8 (mod 16) eight-byte bank units later; the first
-    // exchange, whose stores the one-slot pad was made for (lane j -> 8 j + t), gets its own image - slot1() below.
-    // slot1: the first exchange (pass-1 outputs 8 j + t, read back as j' + t' M / 8) as an 8 x M/8 matrix with rows of M/8 + 4 slots:
-    // stores are lane-linear inside row t, loads take row j' & 7, column (j' >> 3) + t' M / 64 - 32 lanes = 8 rows x 4 columns on
-    // 4 (j' & 7) + (j' >> 3) (mod 32) = 32 distinct bank units.  No address arithmetic beyond a per-lane base either way.
-    static constexpr int ROW1 = M / 8 + 4;
-    __device__ static __forceinline__ constexpr int slot1(int i) { return (SWZ || !PAD64) ? slot(i) : (i & 7) * ROW1 + (i >> 3); }
-    static_assert(SWZ || !PAD64 || 8 * ROW1 <= SLOTS, "the first exchange's image fits the buffer");
 };
 
 // ---- per-lane twiddles, held in registers for the lifetime of the kernel ------------------------------------------
 // A butterfly with base exponent e multiplies input t by W^(e t), t = 1..R-1.
-//   default: only W^e, W^2e, W^4e are stored (exactly rounded table entries) and the other four are single products of two
-//        of them - 12 complex multiplies per radix-8 butterfly, 5 of them on twiddles alone;
-//   MST_FFT2_FULL_TW=1 (n_fft <= 2048 only): all R-1 factors fetched from the table, 7 multiplies.  Measured: no gain
-//        (2048 forward 27.9 -> 30.2 us, 512 backward 51.8 -> 52.4 us) - these passes wait on LDS and barriers, not on the VALU.
-#ifndef MST_FFT2_FULL_TW
-#define MST_FFT2_FULL_TW 0
-#endif
+// Only W^e, W^2e, W^4e are stored (exactly rounded table entries) and the other four are single products of two of them - 12 complex
+// multiplies per radix-8 butterfly, 5 of them on twiddles alone.  (All R-1 factors from the table, 7 multiplies: no gain - 2048 forward
+// 27.9 -> 30.2 us, 512 backward 51.8 -> 52.4 us; these passes wait on LDS and barriers, not on the VALU.)
 template <int N>
 struct LaneTw {
     using S = FftShape<N>;
-    static constexpr bool FULL = MST_FFT2_FULL_TW && N <= 2048;
     static constexpr int LB = ilog2c(S::RL);                       // bases of the last pass
-    float2 mid[S::NP - 2][FULL ? 7 : 3];                           // passes 2 .. NP-1 (radix 8, Ns = 8^(p-1))
-    float2 last[S::NBL][FULL ? S::RL - 1 : LB];                    // pass NP (radix RL, Ns = M / RL, k = j)
+    float2 mid[S::NP - 2][3];   // passes 2 .. NP-1 (radix 8, Ns = 8^(p-1))
+    float2 last[S::NBL][LB];    // pass NP (radix RL, Ns = M / RL, k = j)
     // tw = (cos, -sin)(2 pi t / N), t < N
     __device__ __forceinline__ void init(const float2* __restrict__ tw, int lane) {
         int Ns = 8;
 #pragma unroll
         for (int p = 0; p < S::NP - 2; ++p) {
             const int e = (lane & (Ns - 1)) * (S::M / (Ns * 8));  // W_(8 Ns)^(k t) = W_M^(k t M / (8 Ns))
-            if constexpr (FULL) {
 #pragma unroll
-                for (int t = 1; t < 8; ++t) mid[p][t - 1] = tw[(S::TWSCALE * (e * t)) & (N - 1)];
-            } else {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) mid[p][b] = tw[(S::TWSCALE * (e << b)) & (N - 1)];
-            }
+            for (int b = 0; b < 3; ++b) mid[p][b] = tw[(S::TWSCALE * (e << b)) & (N - 1)];
             Ns *= 8;
         }
 #pragma unroll
         for (int u = 0; u < S::NBL; ++u) {
             const int j = lane + u * S::LG;
-            if constexpr (FULL) {
 #pragma unroll
-                for (int t = 1; t < S::RL; ++t) last[u][t - 1] = tw[(S::TWSCALE * (j * t)) & (N - 1)];
-            } else {
-#pragma unroll
-                for (int b = 0; b < LB; ++b) last[u][b] = tw[(S::TWSCALE * (j << b)) & (N - 1)];
-            }
+            for (int b = 0; b < LB; ++b) last[u][b] = tw[(S::TWSCALE * (j << b)) & (N - 1)];
         }
     }
 };
-template <int R, bool FULL>
+template <int R>
 __device__ __forceinline__ void tw_apply(float2* v, const float2* base) {  // v[t] *= W^(e t)
-    if constexpr (FULL) {
-#pragma unroll
-        for (int t = 1; t < R; ++t) v[t] = cmul(v[t], base[t - 1]);
-    } else {
-        v[1] = cmul(v[1], base[0]);
-        v[2] = cmul(v[2], base[1]);
-        v[3] = cmul(v[3], cmul(base[0], base[1]));
-        if (R == 8) {
-            v[4] = cmul(v[4], base[2]);
-            v[5] = cmul(v[5], cmul(base[0], base[2]));
-            v[6] = cmul(v[6], cmul(base[1], base[2]));
-            v[7] = cmul(v[7], cmul(cmul(base[0], base[1]), base[2]));
-        }
+    v[1] = cmul(v[1], base[0]);
+    v[2] = cmul(v[2], base[1]);
+    v[3] = cmul(v[3], cmul(base[0], base[1]));
+    if (R == 8) {
+        v[4] = cmul(v[4], base[2]);
+        v[5] = cmul(v[5], cmul(base[0], base[2]));
+        v[6] = cmul(v[6], cmul(base[1], base[2]));
+        v[7] = cmul(v[7], cmul(cmul(base[0], base[1]), base[2]));
     }
 }
 
@@ -205,14 +144,13 @@ __device__ __forceinline__ void fft_first(float2* v, float2* __restrict__ buf, i
     using S = FftShape<N>;
     butterfly<8>(v);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) buf[S::slot1(lane * 8 + t)] = v[t];
+    for (int t = 0; t < 8; ++t) buf[S::slot(lane * 8 + t)] = v[t];
 }
-// FIRST: the loads of pass 2, which read the first exchange's image (slot1)
-template <int N, bool FIRST = false>
+template <int N>
 __device__ __forceinline__ void fft_load8(float2* v, const float2* __restrict__ buf, int lane) {
     using S = FftShape<N>;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = buf[FIRST ? S::slot1(lane + t * (S::M / 8)) : S::slot(lane + t * (S::M / 8))];
+    for (int t = 0; t < 8; ++t) v[t] = buf[S::slot(lane + t * (S::M / 8))];
 }
 // middle pass P (2 <= P < NP), Ns = 8^(P-1): twiddle + butterfly + store (after fft_load8 and a barrier)
 template <int N, int P>
@@ -220,7 +158,7 @@ __device__ __forceinline__ void fft_mid_store(float2* v, float2* __restrict__ bu
     using S = FftShape<N>;
     constexpr int Ns = P == 2 ? 8 : 64;
     static_assert(P == 2 || P == 3, "middle passes");
-    tw_apply<8, LaneTw<N>::FULL>(v, tw.mid[P - 2]);
+    tw_apply<8>(v, tw.mid[P - 2]);
     butterfly<8>(v);
     const int k = lane & (Ns - 1);
     const int base = (lane - k) * 8 + k;  // element base + t Ns
@@ -234,7 +172,7 @@ __device__ __forceinline__ void fft_last(float2* v, const float2* __restrict__ b
     const int j = lane + u * S::LG;
 #pragma unroll
     for (int t = 0; t < S::RL; ++t) v[t] = buf[S::slot(j + t * (S::M / S::RL))];
-    tw_apply<S::RL, LaneTw<N>::FULL>(v, tw.last[u]);
+    tw_apply<S::RL>(v, tw.last[u]);
     butterfly<S::RL>(v);
 }
 
@@ -245,11 +183,7 @@ __device__ __forceinline__ void fft_run(float2* v, float2 (*o)[FftShape<N>::RL],
     using S = FftShape<N>;
     fft_first<N>(v, buf, lane);
     group_lds_sync<S::LG>();
-#ifdef MST_FFT2_FIRST_PASS_ONLY
-    for (int u = 0; u < S::NBL; ++u) for (int t = 0; t < S::RL; ++t) o[u][t] = buf[S::slot1(lane + t)];
-    return;
-#endif
-    fft_load8<N, true>(v, buf, lane);
+    fft_load8<N>(v, buf, lane);
     group_lds_sync<S::LG>();
     fft_mid_store<N, 2>(v, buf, tw, lane);
     group_lds_sync<S::LG>();
@@ -271,8 +205,8 @@ __device__ __forceinline__ void fft_run2(float2* va, float2* vb, float2 (*oa)[Ff
     fft_first<N>(va, bufa, lane);
     fft_first<N>(vb, bufb, lane);
     group_lds_sync<S::LG>();
-    fft_load8<N, true>(va, bufa, lane);
-    fft_load8<N, true>(vb, bufb, lane);
+    fft_load8<N>(va, bufa, lane);
+    fft_load8<N>(vb, bufb, lane);
     group_lds_sync<S::LG>();
     fft_mid_store<N, 2>(va, bufa, tw, lane);
     fft_mid_store<N, 2>(vb, bufb, tw, lane);

@@ -79,11 +79,7 @@ struct BasicArgs {
 };
 inline bool basic_path(const mst_console_desc* d) {  // every stage but input fader / panner off, and few enough tracks for the LDS table
     const uint32_t stages = MST_USE_TRACK_EQ | MST_USE_TRACK_COMPRESSOR | MST_USE_FX_BUS | MST_USE_MASTER_BUS | MST_USE_OUTPUT_FADER;
-#ifdef MST_NO_BASIC_PATH
-    return false;
-#else
     return !(d->flags & stages) && (d->flags & MST_USE_TRACK_PANNER) && d->n_tracks <= kBasicMaxTracks && !(d->flags & MST_DEV_MULTIPASS_EQ);
-#endif
 }
 void launch_basic_forward(const BasicArgs& a, hipStream_t stream);
 void launch_basic_backward(const BasicArgs& a, hipStream_t stream);
@@ -101,13 +97,13 @@ struct ZsIn {
     int32_t* status;    // raised to kStatusExchangeTimeout when a wait gives up (may be null)
 };
 // zp != nullptr (forward run only): the all-pole bank of the coefficient-gradient pass rides along, its zero-state chunk
-// end states are written to zp (nsig x 24 x nc_pad) and the backward needs no k_allpole_zs launch.
+// end states are written to zp (nsig x 24 x nc_pad) and the backward starts at the all-pole carry scan.
 // pw1 (in-wave scan tables of these rows) != nullptr: SCAN1 kernels, no carry-scan launch between zs and run (mst_eq.hip);
 // agg (nsig x 12 x kMaxTiles1) carries the tile aggregates from the zs launch to the run launch
 void launch_cascade(int dir, bool run, const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc,
                     int split, const float* s0, float* z, int nc_pad, int64_t n, int nsig, hipStream_t stream,
                     const float* pw1 = nullptr, int ntiles = 0, float* agg = nullptr, float* zp = nullptr);
-// forward run of mono rows fused with the compressor's zero-state block aggregates (replaces k_comp_zs<1>)
+// forward run of mono rows fused with the compressor's zero-state block aggregates (no separate zero-state pass over the EQ output)
 void launch_cascade_run_gc(const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc, int split,
                            const float* s0, int nc_pad, int64_t n, int nsig, float* zs_comp, int nblk_comp, hipStream_t stream,
                            const float* pw1 = nullptr, int ntiles = 0, float* agg = nullptr, float* zp = nullptr, const ZsIn* zi = nullptr);
@@ -120,10 +116,6 @@ void launch_master_run_apscan(const float* in, int64_t in_stride, float* out, in
                               int64_t n, int nsig, hipStream_t stream, const float* pw1, int ntiles, float* agg, float* zp,
                               const float* sc_z, float* sc_s0, const float* sc_tab, int sc_jobs, int sc_nc, int sc_sh, int dir = EQ_FWD,
                               const ZsIn* zi = nullptr);  // zi (wz != null): the master rows' zero-state pass runs inside the launch too (no k_eq_zs_mfma before it)
-void launch_allpole_zs(const float* u, int64_t u_stride, const float* rc, int split, float* z, int nc_pad, int64_t n, int nsig,
-                       hipStream_t stream);
-void launch_coefgrad(const float* u, int64_t u_stride, const float* g, int64_t g_stride, const float* rc, int split,
-                     const float* s0, int nc_pad, float* part, int64_t n, int nsig, hipStream_t stream);
 
 // ---- mst_scan.hip
 void launch_scan12(bool reverse, const float* z, float* s0, const float* tab, int split, int nc, int nc_pad, int K, int nsig,
@@ -156,7 +148,7 @@ struct MasterApplyArgs {
     int nc_pad, lookahead, comp_on;
     int64_t n;
     int aligned;
-    gran_t* gran;        // (bs, nblk) zeroed granules (+ their near copies gran_near granules later): the smoother's block aggregates are exchanged inside this launch (no k_comp_zs); null = read s0
+    gran_t* gran;        // (bs, nblk) zeroed granules (+ their near copies gran_near granules later): the smoother's block aggregates are exchanged inside this launch; null = read s0
     int64_t gran_near;
     int32_t* status;     // raised to kStatusExchangeTimeout when an exchange wait gives up (may be null)
 };
@@ -167,7 +159,7 @@ struct CompBwdArgs {
     const float* gs;      // (rows, stride) saved smoothed gain (dB)
     const float* rc;      // (rows, RC_STRIDE)
     const float* s0;      // run pass: adjoint smoother state entering each chunk from the right
-    float* zq;            // (rows, nc_pad) out of the zs pass
+    float* zq;            // (rows, nc_pad) not used by the run pass (the field keeps the kernels' argument layout)
     float* du;            // (rows*NCH, stride) out of the run pass: cotangent of the compressor input
     float* part;          // (rows, nblk, CP_COUNT) out of the run pass
     const float* gup;     // tracks: grad wrt stereo bus ; master: grad wrt mix ; (bs,2,gup_stride)
@@ -178,7 +170,7 @@ struct CompBwdArgs {
     int T, nc_pad, lookahead, comp_on;
     int64_t n;
     int aligned;
-    // tracks, MST_FUSE_COEFGRAD: the run pass also forms the coefficient-gradient sums of its 2048 samples (else ep = null)
+    // the run pass also forms the coefficient-gradient sums of its 2048 samples (else ep = null)
     const float* ap_s0;   // all-pole states entering every 64-sample chunk (rows, 24, ap_nc_pad)
     int ap_nc_pad;
     float* ep;            // (rows, nblkC, EP_COUNT)
@@ -191,13 +183,10 @@ struct CompBwdArgs {
     gran_t* gran;         // (rows, nblk) zeroed granules (+ near copies gran_near granules later): the run pass publishes / awaits the block aggregates itself (no zs launch); null = read s0
     int64_t gran_near;
     int32_t* status;      // raised to kStatusExchangeTimeout when an exchange wait gives up (may be null)
-    int mw_split;         // k_comp_bwd_mix only (set by launch_comp_bwd): workgroups the tracks of one mix are dealt to (1 or 2)
 };
-void launch_comp_zs(int nch, const float* u, int64_t stride, const float* rc, float* zs, int nc_pad, int64_t n, int rows,
-                    hipStream_t stream);
 void launch_apply_tracks(const TrackApplyArgs& a, int bs, hipStream_t stream);
 void launch_apply_master(const MasterApplyArgs& a, int bs, hipStream_t stream);
-void launch_comp_bwd(bool master, bool run, const CompBwdArgs& a, int rows, hipStream_t stream);
+void launch_comp_bwd(bool master, const CompBwdArgs& a, int rows, hipStream_t stream);
 
 // ---- mst_fx.hip: the fx bus (noise-shaped reverberation on a send bus); offsets are float offsets into the workspace
 struct FxPlan {

@@ -51,9 +51,6 @@ __device__ __forceinline__ void matvec_acc(const float* M, const float* v, float
 //   C[k][jj][4]  at 144 + (k (k-1) / 2 + jj) 4     P_k,jj for jj < k
 //   Dp[k][q][4]  at 208 + (16 k + q) 4             D_k^(q+1), q = 0..15
 constexpr int kTriFloats = 592;
-#ifndef MST_SCAN_PACKED
-#define MST_SCAN_PACKED 1  // the LDS image of the tables holds every 2x2 block column-major (wave_scan_tri below)
-#endif
 struct TabRegs {
     float4 v[3];
 };
@@ -68,7 +65,7 @@ __device__ __forceinline__ void tab_stash(const TabRegs& r, float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int q = lane + 64 * k;
-        if (q < kTriFloats / 4) *reinterpret_cast<float4*>(lds + 4 * q) = MST_SCAN_PACKED ? make_float4(r.v[k].x, r.v[k].z, r.v[k].y, r.v[k].w) : r.v[k];
+        if (q < kTriFloats / 4) *reinterpret_cast<float4*>(lds + 4 * q) = make_float4(r.v[k].x, r.v[k].z, r.v[k].y, r.v[k].w);
     }
 }
 // value of the lane CTRL points at; 0 where that lane does not exist (row / wave edge)
@@ -88,8 +85,7 @@ using scan_f2 = f2;
 struct Mat2c { scan_f2 c0, c1; };  // columns
 __device__ __forceinline__ Mat2c mat_at(const float* __restrict__ tab, int at) {
     const float4 m = *reinterpret_cast<const float4*>(tab + at);
-    if (MST_SCAN_PACKED) return Mat2c{scan_f2{m.x, m.y}, scan_f2{m.z, m.w}};
-    return Mat2c{scan_f2{m.x, m.z}, scan_f2{m.y, m.w}};  // row-major image
+    return Mat2c{scan_f2{m.x, m.y}, scan_f2{m.z, m.w}};
 }
 __device__ __forceinline__ scan_f2 mat_acc(const Mat2c& m, float o0, float o1, scan_f2 f) {  // f + M (o0, o1)
     return f2_fma(m.c0, scan_f2{o0, o0}, f2_fma(m.c1, scan_f2{o1, o1}, f));

@@ -7,9 +7,6 @@
 // :353-460; biquad design + compressor constants + pan law = dasp-pytorch 0.0.1.
 #include "mst_kernels.h"
 
-#ifndef MST_PREP_STOP
-#define MST_PREP_STOP 0  // timing diagnostics only (wrong results): k_prep returns after stage 1 / 2 / 3
-#endif
 namespace mst {
 
 // ---------------------------------------------------------------------------------------------
@@ -280,9 +277,6 @@ __global__ __launch_bounds__(320) void k_prep(PrepArgs a) {
         rc[RC_AP + 3 * tid + 2] = 1.0f / b0;
     }
 
-#if MST_PREP_STOP == 1
-    return;
-#endif
     // ---- one-sample transition matrices of the forward and the adjoint cascade (zero input)
     double c64[30];
     for (int i = 0; i < 30; ++i) c64[i] = (double)coef[i];
@@ -329,9 +323,6 @@ __global__ __launch_bounds__(320) void k_prep(PrepArgs a) {
         cur ^= 1;
     }
     if (mat_lane) pw[0 * 144 + e] = (float)mats[grp][cur][e];
-#if MST_PREP_STOP == 2
-    return;
-#endif
     if (a.eq1) {
         // forward: an impulse at sample j of the chunk is 63 - j steps from its end; adjoint (reverse time): j steps
         float* wzF = is_master ? a.wzF_m + (int64_t)mrow * kWz : a.wzF_t + (int64_t)row * kWz;
@@ -374,9 +365,6 @@ __global__ __launch_bounds__(320) void k_prep(PrepArgs a) {
             __syncthreads();
             cur ^= 1;
         }
-#if MST_PREP_STOP == 3
-        return;
-#endif
         __syncthreads();  // the parked diagonal blocks of M^64
         for (int item = tid; item < 12 * (kPow1 - 1 - kPow1Full); item += 320) {
             const int nj = kPow1 - 1 - kPow1Full, blk = item / nj, jj = item % nj, g2 = blk / 6, k = blk % 6;

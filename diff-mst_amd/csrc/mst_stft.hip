@@ -14,9 +14,6 @@
 // (incl. the reflect-padding fold-back) uses hardware float atomics into grad_pred.
 #include "mst_kernels.h"
 #include "mst_stft.h"
-#ifndef MST_STFT_UNROLL_STAGES
-#define MST_STFT_UNROLL_STAGES 1  // stage loops of the transforms unrolled so that the stage constants fold (386 -> 368 us; 0 = rolled, for A/B)
-#endif
 
 namespace mst {
 
@@ -59,11 +56,7 @@ __device__ __forceinline__ float2* lds_fft(float2* a, float2* b, const Twiddles<
         __syncthreads();
     }
     constexpr int q = NFFT >> 2;
-#if MST_STFT_UNROLL_STAGES
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
     for (; Ns < NFFT; Ns <<= 2) {
         const int tstep = NFFT / (4 * Ns);
 #pragma unroll
@@ -138,11 +131,7 @@ __device__ __forceinline__ void fft_dif(float2* buf, const Twiddles<N>& T, int t
         }
         __syncthreads();
     }
-#if MST_STFT_UNROLL_STAGES
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
     for (int L = M / 4; L >= 1; L >>= 2) {
         const int tstep = N / (4 * L);
 #pragma unroll
@@ -177,11 +166,7 @@ __device__ __forceinline__ void fft_dit(float2* buf, const Twiddles<N>& T, int t
     constexpr int LG = ilog2(N);
     constexpr bool ODD = LG & 1;
     constexpr int M = ODD ? N / 2 : N;
-#if MST_STFT_UNROLL_STAGES
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
     for (int L = 1; L < M; L <<= 2) {
         const int tstep = N / (4 * L);
 #pragma unroll
@@ -435,7 +420,7 @@ __global__ __launch_bounds__(stft_threads(NFFT)) void k_stft_bwd(StftArgs a) {
     }
 }
 
-// ---- the same two kernels on the in-place transform (used for n_fft = 8192) -------------------------
+// ---- the backward on the in-place transform (used for n_fft = 8192) ---------------------------------
 constexpr int kIpThreads = 512;
 
 // frame f as z = w (x + i y) with fft_dif's leading radix-2 stage applied on the way in (n_fft with odd log2):
@@ -454,49 +439,6 @@ __device__ __forceinline__ void load_frame_ip(float2* buf, const float* __restri
         const float2 u0 = make_float2(w0 * x[i0], w0 * y[i0]), u1 = make_float2(w1 * x[i1], w1 * y[i1]);
         buf[lds_swz<LG>(j)] = cadd(u0, u1);
         buf[lds_swz<LG>(j + h)] = cmul(csub(u0, u1), tw[j]);
-    }
-}
-
-template <int NFFT>
-__global__ __launch_bounds__(kIpThreads) void k_stft_fwd_ip(StftArgs a) {
-    constexpr int THREADS = kIpThreads;
-    __shared__ __attribute__((aligned(16))) float2 buf[NFFT];
-    __shared__ float red[THREADS / 64][4];
-    __shared__ Twiddles<NFFT> twd;
-    const int tid = threadIdx.x, row = blockIdx.y;
-    const ResInfo r = a.r;
-    stage_twiddles<NFFT>(twd, reinterpret_cast<const float2*>(a.tables + r.tw_off), tid, THREADS);
-    const float* win = a.tables + r.win_off;
-    const float* x = a.pred + (int64_t)row * a.n;
-    const float* y = a.target + (int64_t)row * a.n;
-    float s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f;
-    const int f0 = blockIdx.x * r.frames_per_wg;
-    for (int f = f0; f < f0 + r.frames_per_wg && f < r.n_frames; ++f) {
-        load_frame_ip<NFFT>(buf, x, y, win, reinterpret_cast<const float2*>(a.tables + r.tw_off), f, r, a.n, tid);
-        __syncthreads();
-        fft_dif<NFFT, THREADS, true>(buf, twd, tid);
-        for (int k = tid; k < r.n_bins; k += THREADS) {
-            float2 X, Y;
-            split_xy<NFFT, true>(buf, k, X, Y);
-            const float xm = sqrtf(fmaxf(X.x * X.x + X.y * X.y, a.eps));
-            const float ym = sqrtf(fmaxf(Y.x * Y.x + Y.y * Y.y, a.eps));
-            const float d = ym - xm;
-            s1 = fmaf(d, d, s1);
-            s2 = fmaf(ym, ym, s2);
-            s3 += fabsf(__builtin_amdgcn_logf(xm) - __builtin_amdgcn_logf(ym));  // log2; scaled by ln2 below
-            s4 += fabsf(d);
-        }
-        __syncthreads();
-    }
-    s3 *= kLn2;
-    const int wave = tid >> 6, lane = tid & 63;
-    s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3); s4 = wave_sum(s4);
-    if (lane == 0) { red[wave][0] = s1; red[wave][1] = s2; red[wave][2] = s3; red[wave][3] = s4; }
-    __syncthreads();
-    if (tid < 4) {
-        float v = 0.f;
-        for (int w = 0; w < THREADS / 64; ++w) v += red[w][tid];
-        a.part[((int64_t)row * gridDim.x + blockIdx.x) * 4 + tid] = v;
     }
 }
 
@@ -694,17 +636,11 @@ Plan make_plan(const mst_mrstft_desc* d) {
         p.win[i] = d->win_length[i];
         // strips of 2 frames measured best on MI355X at cfg #2 (1: 423, 2: 411, 4: 443, 8: 455, 16: 566 us per fwd+bwd)
         r.frames_per_wg = ((int64_t)r.n_frames * d->rows >= 1024) ? 2 : 1;
-#ifdef MST_STFT_FPW
-        r.frames_per_wg = MST_STFT_FPW;
-#endif
         p.n_groups[i] = (r.n_frames + r.frames_per_wg - 1) / r.frames_per_wg;
         // round-2 kernels: the reference's shape of resolution (hop = n_fft / 2, full-length window), rows long enough
         // that no frame reflects at both ends, whole hops per row (the owner-computes overlap-add assumes it)
         p.engine2[i] = (nf == 512 || nf == 2048 || nf == 8192) && r.hop * 2 == nf && d->win_length[i] == nf &&
                        d->n_samples >= 2 * (int64_t)nf && d->n_samples % r.hop == 0;
-#ifdef MST_STFT_ROUND1
-        p.engine2[i] = false;
-#endif
         if (p.engine2[i]) {
             // balanced strips of ~8 / 4 / 2 frames (one workgroup each): consecutive frames share half their samples
             // fused forward with the kept spectra (one box, us): (4, 4) 83.8; (3, 4) 80.0; (3, 6) 79.6; (3, 7) 80.0; (4, 6) 78.6 vs 81.5; (6, 4) 83.6 vs
@@ -756,27 +692,15 @@ Plan make_plan(const mst_mrstft_desc* d) {
         if (p.engine2[i]) {
             p.ymag_off[i] = p.ws_floats;
             p.ws_floats += round_up((int64_t)d->rows * p.res[i].n_frames * p.res[i].n_bins, 64);
-            if (stft2_keeps_spectrum(p.res[i].n_fft)) {
-                p.xspec_off[i] = p.ws_floats;
-                p.ws_floats += round_up((int64_t)d->rows * p.res[i].n_frames * p.res[i].n_bins * 2, 64);
-            }
+            p.xspec_off[i] = p.ws_floats;
+            p.ws_floats += round_up((int64_t)d->rows * p.res[i].n_frames * p.res[i].n_bins * 2, 64);
         }
     }
     p.ok = true;
     return p;
 }
 // n_fft = 8192: the backward runs on the in-place kernel (two workgroups per CU: 105 vs 128 us at cfg #2), the
-// forward stays on the two-buffer kernel (in place it measured 69-78 vs 62 us).  Build-time A/B switches:
-// -DMST_STFT_PINGPONG -> two-buffer kernels everywhere; -DMST_STFT_INPLACE_FWD -> in-place forward as well.
-static constexpr bool inplace_8192(bool forward) {
-#if defined(MST_STFT_PINGPONG)
-    return false;
-#elif defined(MST_STFT_INPLACE_FWD)
-    return true;
-#else
-    return !forward;
-#endif
-}
+// forward stays on the two-buffer kernel (in place it measured 69-78 vs 62 us)
 #define MST_FOR_NFFT(nf, CALL) \
     switch (nf) {               \
         case 128: CALL(128); break;   \
@@ -835,23 +759,17 @@ static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, co
     la.totals = totals;
     la.gtotals = gtotals;
     la.world = gtotals ? world : 1;
-#ifndef MST_MRSTFT_FUSE_FINISH
-#define MST_MRSTFT_FUSE_FINISH 1
-#endif
     // single-rank call: row sums, loss and backward coefficients in ONE launch (k_mrstft_finish) whose ticket the first transform
     // launch zeroes - that launch has to be a round-2 kernel
-    const bool fuse = MST_MRSTFT_FUSE_FINISH && stages == 3 && !totals && !gtotals && p.engine2[0];
+    const bool fuse = stages == 3 && !totals && !gtotals && p.engine2[0];
     for (int i = 0; i < d->n_res; ++i) {
         la.n_groups[i] = p.n_groups[i];
         la.part_off[i] = p.part_off[i];
         la.count[i] = (float)((double)d->rows * p.res[i].n_bins * p.res[i].n_frames);
     }
-#ifndef MST_STFT3_FUSE
-#define MST_STFT3_FUSE 1  // A/B switch: 0 = one forward launch per resolution
-#endif
     // the reference's three resolutions, all on the round-2 kernels: ONE forward launch (k_stft3_fwd, mst_stft2.hip)
     int role[3] = {-1, -1, -1};
-    bool fuse3 = MST_STFT3_FUSE && (stages & 1) && d->n_res == 3;
+    bool fuse3 = (stages & 1) && d->n_res == 3;
     for (int i = 0; i < d->n_res && fuse3; ++i) {
         const int which = p.res[i].n_fft == 8192 ? 0 : (p.res[i].n_fft == 2048 ? 1 : (p.res[i].n_fft == 512 ? 2 : -1));
         if (which < 0 || !p.engine2[i] || role[which] >= 0) fuse3 = false;
@@ -899,9 +817,7 @@ static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, co
 #define MST_LAUNCH_FWD(NF) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_fwd<NF>), grid, dim3(stft_threads(NF)), 0, stream, a)
         if (p.engine2[i]) {
             launch_stft2_fwd(a, p.n_groups[i], d->rows, stream);
-        } else if (a.r.n_fft == 8192 && inplace_8192(true))
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_fwd_ip<8192>), grid, dim3(kIpThreads), 0, stream, a);
-        else
+        } else
             MST_FOR_NFFT(a.r.n_fft, MST_LAUNCH_FWD)
     }
     if (fuse) {
@@ -955,16 +871,13 @@ extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, 
         if (zero && !handover) (void)hipMemsetAsync(grad_pred, 0, (size_t)d->rows * d->n_samples * sizeof(float), stream);
         bool written = zero;
         bool pending = handover;  // the parked seam halves still wait for a halo-mode launch
-#ifndef MST_STFT2_BWD_FUSE
-#define MST_STFT2_BWD_FUSE 1  // A/B switch: 0 = one backward launch per resolution
-#endif
         // the 512- and the 2048-point resolution (halo mode both) in one launch: k_stft2_bwd_512_2048, mst_stft2.hip
         int i512 = -1, i2048 = -1;
         for (int i = 0; i < d->n_res; ++i) {
             if (p.res[i].n_fft == 512) i512 = i512 < 0 ? i : -2;
             if (p.res[i].n_fft == 2048) i2048 = i2048 < 0 ? i : -2;
         }
-        const bool fuse2 = MST_STFT2_BWD_FUSE && i512 >= 0 && i2048 >= 0 && stft2_bwd_can_fuse(d->n_samples);
+        const bool fuse2 = i512 >= 0 && i2048 >= 0 && stft2_bwd_can_fuse(d->n_samples);
         StftArgs held{};  // the 512-point launch's arguments, kept until the 2048-point resolution comes up
         for (int pass = 0; pass < 2; ++pass) {
             for (int k = 0; k < d->n_res; ++k) {
@@ -1023,10 +936,12 @@ extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, 
         // three LDS buffers (pairing two frames per inverse FFT) fit up to n_fft = 4096; 8192 runs one frame per workgroup
         const bool pair = a.r.n_fft <= 4096;
         const dim3 grid(pair ? (a.r.n_frames + 1) / 2 : a.r.n_frames, d->rows);
+        // (both arms are instantiated for every size, and k_stft_bwd<8192, false> is never launched: the surviving kernels' machine code
+        // depends on the order in which their shared transforms are instantiated, so the macro stays as it is - DESIGN 14)
 #define MST_LAUNCH_BWD(NF)                                                                                             \
     if (NF <= 4096) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_bwd<NF, (NF <= 4096)>), grid, dim3(stft_threads(NF)), 0, stream, a); \
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_bwd<NF, false>), grid, dim3(stft_threads(NF)), 0, stream, a)
-        if (a.r.n_fft == 8192 && inplace_8192(false))
+        if (a.r.n_fft == 8192)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_bwd_ip<8192>), grid, dim3(kIpThreads), 0, stream, a);
         else
             MST_FOR_NFFT(a.r.n_fft, MST_LAUNCH_BWD)

@@ -109,8 +109,9 @@ def test_console_golden(path, console, dev, record):
     # One documented exception to the factor 2: full_2x4x16384 (measured 2.13).  tools/dbg_golden_grad.py locates it in ONE section - the
     # high shelf of track 2 at 13.8 kHz, Q 3.7, +8.4 dB, whose fp32 design loses digits in 1 + cos w0: its frequency / gain gradients sit
     # 4.2e-3 / 1.7e-3 of the total norm from float64 for HIP and 1.4e-3 / 8.6e-4 for the reference's fp32 autograd.  Forming the
-    # coefficient-gradient sums and the all-pole recurrences in float64 (-DMST_CG_F64) does not move it: it is the gradient at the
-    # fp32-rounded coefficients, not round-off of the kernels.  Every other fixture and every three-way test keeps the factor 2.
+    # coefficient-gradient sums and the all-pole recurrences in float64 does not move it ("The coefficient-gradient sums
+    # in float64"): it is the gradient at the fp32-rounded coefficients, not round-off of the kernels.  Every other fixture and every
+    # three-way test keeps the factor 2.
     factor = {"console_full_2x4x16384.npz": 2.5}.get(os.path.basename(path), 2.0)
     for key, hip_g in (("grad_track_params", out["g_tp"]), ("grad_master_bus_params", out["g_mp"])):
         if np.abs(g[key]).max() == 0:
