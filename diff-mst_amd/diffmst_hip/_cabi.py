@@ -25,7 +25,7 @@ NO_RANGE_CHECK = 0x400
 BWD_PREPARED = 0x800
 SPLIT_BATCH = 0x1000
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class ConsoleDesc(C.Structure):
@@ -153,6 +153,11 @@ SIGNATURES = {
                                           C.c_size_t, _P]),
     "mst_loudness_normalize": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float,
                                          _P, _P]),
+    "mst_resample_tables_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mst_resample_init_tables": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    "mst_resample_out_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "mst_resample_forward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mst_resample_backward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (C.c_int, [_P, _P]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

@@ -197,9 +197,129 @@ class LoudnessMeter:
 
 
 # ------------------------------------------------------------------------------------------------
+# Sample-rate conversion on the device (mst_resample.hip).  torchaudio.functional.resample with its defaults (sinc_interp_hann,
+# lowpass_filter_width 6, rolloff 0.99); PARITY UNPINNED: restated from torchaudio's published source, never run against the
+# package.
+# ------------------------------------------------------------------------------------------------
+_RESAMPLE_TABLES = {}
+
+
+def _int_rate(value, name):
+    """Sample rates are ints or integral floats (torchaudio converts both with int()); anything else is refused."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or value != value or value in (float("inf"), float("-inf")):
+        raise ValueError(f"{name} must be an integer sample rate, got {value!r}")
+    if float(value) != int(value):
+        raise ValueError(f"{name} must be an integer sample rate, got {value!r} (fractional rates are not supported)")
+    if int(value) <= 0:
+        raise ValueError(f"{name} must be positive, got {value!r}")
+    return int(value)
+
+
+def _resample_tables(device, orig_freq, new_freq):
+    """Both coefficient tables (forward and adjoint) of a ratio: built once per (device, o, n)."""
+    import math
+
+    g = math.gcd(orig_freq, new_freq)
+    key = (str(device), orig_freq // g, new_freq // g)
+    t = _RESAMPLE_TABLES.get(key)
+    if t is None:
+        lib = _hip.lib()
+        nbytes = lib.mst_resample_tables_bytes(orig_freq, new_freq)
+        if nbytes == 0:
+            raise ValueError(f"unsupported resampling ratio {orig_freq} -> {new_freq}: reduced to {key[1]}:{key[2]}, the device "
+                             "resampler takes reduced rates up to 1024 and at most 132 taps per output sample")
+        t = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _hip.check(lib.mst_resample_init_tables(orig_freq, new_freq, _cabi.ptr(t), _hip.current_stream_ptr(device)),
+                       "mst_resample_init_tables")
+        _RESAMPLE_TABLES[key] = t
+    return t
+
+
+def _time_rows(x):
+    """``(..., time)`` -> a ``(rows, time)`` fp32 view with unit sample stride (copies only when it has to)."""
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(-1) != 1:
+        x = x.contiguous()
+    return x.reshape(-1, x.shape[-1])  # a view whenever the leading dimensions collapse (a last-dimension slice does)
+
+
+class _Resample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, orig_freq, new_freq):
+        lib = _hip.lib()
+        dev = x.device
+        tables = _resample_tables(dev, orig_freq, new_freq)
+        rows = _time_rows(x.detach())
+        n_rows, n = rows.shape
+        n_out = lib.mst_resample_out_samples(n, orig_freq, new_freq)
+        if n_out <= 0:
+            raise ValueError(f"unsupported resample call: {n} samples, {orig_freq} -> {new_freq}")
+        y = torch.empty(n_rows, n_out, dtype=torch.float32, device=dev)
+        if n_rows:
+            with torch.cuda.device(dev):
+                _hip.check(lib.mst_resample_forward(_cabi.ptr(rows), n_rows, n, rows.stride(0), orig_freq, new_freq, _cabi.ptr(tables),
+                                                    _cabi.ptr(y), _hip.current_stream_ptr(dev)), "mst_resample_forward")
+        ctx.rates = (orig_freq, new_freq)
+        ctx.in_shape, ctx.in_dtype = x.shape, x.dtype
+        return y.view(*x.shape[:-1], n_out).to(x.dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        lib = _hip.lib()
+        orig_freq, new_freq = ctx.rates
+        dev = g.device
+        n = ctx.in_shape[-1]
+        g2 = g.float().contiguous().view(-1, g.shape[-1])
+        gx = torch.empty(g2.shape[0], n, dtype=torch.float32, device=dev)
+        if g2.shape[0]:
+            with torch.cuda.device(dev):
+                _hip.check(lib.mst_resample_backward(_cabi.ptr(g2), g2.shape[0], n, orig_freq, new_freq,
+                                                     _cabi.ptr(_resample_tables(dev, orig_freq, new_freq)), _cabi.ptr(gx),
+                                                     _hip.current_stream_ptr(dev)), "mst_resample_backward")
+        return gx.view(ctx.in_shape).to(ctx.in_dtype), None, None
+
+
+def resample(waveform: torch.Tensor, orig_freq, new_freq):
+    """``torchaudio.functional.resample(waveform, orig_freq, new_freq)`` (defaults: Hann-windowed sinc interpolation, width 6,
+    roll-off 0.99) of a device tensor ``(..., time)`` -> ``(..., ceil(time * new / orig))``, differentiable with respect to
+    ``waveform``.  Equal rates return ``waveform`` itself.  The arithmetic is fp32 with coefficients evaluated in float64 on the
+    host; other floating dtypes are converted and the result is cast back, so a float64 input is computed in fp32 here
+    (torchaudio would compute it in float64).  A last-dimension slice of a wider buffer is read in place.  The output length is
+    evaluated in integers (torchaudio: through a float32 tensor, one sample off in rare cases above 2^24 samples)."""
+    orig_freq, new_freq = _int_rate(orig_freq, "orig_freq"), _int_rate(new_freq, "new_freq")
+    if not isinstance(waveform, torch.Tensor) or not waveform.is_floating_point():
+        raise TypeError("resample expects a floating-point tensor (..., time)")
+    if orig_freq == new_freq:
+        return waveform
+    _hip.require_cuda(waveform)
+    if waveform.dim() < 1 or waveform.shape[-1] < 1:
+        raise ValueError("expected a (..., time) tensor with at least one sample")
+    _resample_tables(waveform.device, orig_freq, new_freq)  # an unsupported ratio raises before anything is launched
+    return _Resample.apply(waveform, orig_freq, new_freq)
+
+
+class Resample(torch.nn.Module):
+    """``torchaudio.transforms.Resample(orig_freq, new_freq)`` with its default method: ``Resample(a, b)(x) = resample(x, a, b)``."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000):
+        super().__init__()
+        self.orig_freq, self.new_freq = _int_rate(orig_freq, "orig_freq"), _int_rate(new_freq, "new_freq")
+
+    def forward(self, waveform: torch.Tensor) -> torch.Tensor:
+        return resample(waveform, self.orig_freq, self.new_freq)
+
+    def extra_repr(self):
+        return f"orig_freq={self.orig_freq}, new_freq={self.new_freq}"
+
+
+# ------------------------------------------------------------------------------------------------
 # Inference driver (reference mst/utils.py:32-258): forward-only, batch 1, long songs
 # ------------------------------------------------------------------------------------------------
 ANALYSIS_LEN = 262144  # reference mst/utils.py:66
+SAMPLE_RATE = 44100    # the rate the model, the meter and the console work at
 
 
 def _default_loudness_fn(sample_rate=44100):
@@ -214,7 +334,8 @@ def _default_loudness_fn(sample_rate=44100):
 
 
 def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module, mix_console: torch.nn.Module,
-                track_start_idx: int = 0, ref_start_idx: int = 0, loudness_fn=None, device=None, verbose: bool = False):
+                track_start_idx: int = 0, ref_start_idx: int = 0, loudness_fn=None, device=None, verbose: bool = False,
+                track_sample_rate=44100, ref_sample_rate=44100):
     """Reference ``mst.utils.run_diffmst`` (mst/utils.py:32-173) on the HIP console.
 
     ``tracks (1, T, n)``, ``ref (1, 2, n_ref)`` (host or device tensors) ->
@@ -229,7 +350,10 @@ def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module,
     ``pred_mix`` comes back on ``tracks.device``; ``loudness_fn(ndarray (n, 1)) -> float`` replaces the
     pyloudnorm meter where that package is absent (it is host-side in the reference too); ``loudness_fn="device"`` measures and
     normalises on the device instead (``integrated_loudness`` / ``loudness_normalize`` above - BS.1770 as pyloudnorm computes it,
-    parity unpinned): one meter call over all tracks, and the only host read is the mask of the tracks that survive."""
+    parity unpinned): one meter call over all tracks, and the only host read is the mask of the tracks that survive;
+    ``track_sample_rate`` / ``ref_sample_rate`` other than 44100 convert that input to 44100 Hz on the device first (``resample``
+    above - what the reference's scripts do with torchaudio before they call this function, scripts/run.py:78-79, :108-109), so
+    ``track_start_idx`` / ``ref_start_idx`` index the 44100 Hz signals and ``pred_mix`` is returned at 44100 Hz."""
     if tracks.dim() != 3 or tracks.shape[0] != 1:
         raise ValueError("tracks must be (1, num_tracks, seq_len)")  # the reference's squeeze(0) / zeros(1, 2, n) fix bs = 1
     if loudness_fn is None:
@@ -243,6 +367,11 @@ def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module,
         # host path, so the model follows the audio onto the device - in place, like nn.Module.to
         if any(t.device != device for t in (*model.parameters(), *model.buffers())):
             model.to(device)
+    out_device = tracks.device
+    if _int_rate(track_sample_rate, "track_sample_rate") != SAMPLE_RATE:
+        tracks = resample(tracks.detach().to(device=device, dtype=torch.float32), track_sample_rate, SAMPLE_RATE)
+    if _int_rate(ref_sample_rate, "ref_sample_rate") != SAMPLE_RATE:
+        ref = resample(ref.detach().to(device=device, dtype=torch.float32), ref_sample_rate, SAMPLE_RATE)
     n = tracks.shape[-1]
     if n >= ANALYSIS_LEN:
         analysis_tracks = tracks[..., track_start_idx:track_start_idx + ANALYSIS_LEN]
@@ -256,7 +385,7 @@ def run_diffmst(tracks: torch.Tensor, ref: torch.Tensor, model: torch.nn.Module,
         norm_tracks, norm_analysis = _normalize_tracks_on_device(tracks, n, track_start_idx, device, verbose)
     else:
         norm_tracks, norm_analysis = _normalize_tracks_on_host(tracks, analysis_tracks, loudness_fn, device, verbose)
-    return _mix_windows(tracks, norm_tracks, norm_analysis, analysis_ref, model, mix_console, device, n)
+    return _mix_windows(out_device, norm_tracks, norm_analysis, analysis_ref, model, mix_console, device, n)
 
 
 def _normalize_tracks_on_device(tracks, n, track_start_idx, device, verbose):
@@ -299,7 +428,7 @@ def _normalize_tracks_on_host(tracks, analysis_tracks, loudness_fn, device, verb
     return norm_tracks, norm_analysis
 
 
-def _mix_windows(tracks, norm_tracks, norm_analysis, analysis_ref, model, mix_console, device, n):
+def _mix_windows(out_device, norm_tracks, norm_analysis, analysis_ref, model, mix_console, device, n):
     # ---- one parameter estimate from the analysis audio
     pred_track_params, pred_fx_bus_params, pred_master_bus_params = model(norm_analysis, analysis_ref.float().to(device))
 
@@ -319,7 +448,7 @@ def _mix_windows(tracks, norm_tracks, norm_analysis, analysis_ref, model, mix_co
             )
             m = mix_w.shape[-1]  # the last window is shorter: the reference pads it to 262144 before the fade
             pred_mix[..., i:i + m] += mix_w * (first if i == 0 else window)[:m]
-    return (pred_mix.to(tracks.device), *dicts)
+    return (pred_mix.to(out_device), *dicts)
 
 
 def load_diffmst(config_path: str, ckpt_path: str, map_location: str = "cpu"):

@@ -285,6 +285,33 @@ int mst_loudness_normalize(const float* x, float* y, const float* lufs, int32_t 
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sample-rate conversion (ABI v11) with the semantics of torchaudio.functional.resample(x, orig_freq, new_freq) at its defaults
+ * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) - what every script of the reference applies to the tracks and the
+ * reference mix before anything else (scripts/run.py:78-79, scripts/online.py:223-226, mst/callbacks/mix.py:52).  PARITY UNPINNED: a
+ * restatement of torchaudio's published source, not checked against the package.  With o = orig / gcd, n = new / gcd:
+ *   y[j n + i] = sum_k h[i][k] xpad[j o + k],  h in float64 as torchaudio writes it, rounded once to fp32; only taps whose fp32
+ *   value is exactly 0 are skipped.  n_out = mst_resample_out_samples = ceil(n n_samples / o), in integers (torchaudio evaluates
+ *   this through a float32 tensor, which can differ by one sample above 2^24 output samples; that is not imitated).
+ *   x        `rows` signals of n_samples fp32 samples, unit sample stride, row_stride elements apart, any 4-byte alignment
+ *   tables   mst_resample_tables_bytes(orig, new) bytes filled once by mst_resample_init_tables.  They open with 16 int32 words:
+ *            o, n, width, T (taps per output), frames per tile of the forward (a tile is that many x n consecutive outputs, staged
+ *            and computed as one piece by a workgroup), E (taps per input sample of the adjoint), frames per tile of the adjoint
+ *            (x o input samples), the word offsets of the two coefficient tables; the rest is reserved
+ *   y        dense (rows, n_out), every sample written once
+ * mst_resample_backward is the adjoint: grad_y dense (rows, n_out) -> grad_x dense (rows, n_samples), from the same fp32
+ * coefficients.  Supported: reduced o, n <= 1024, o != n (equal rates are the identity: mst_resample_out_samples returns n_samples
+ * and there is nothing to launch), at most 132 taps per output (o / n up to ~10.8), 1 <= n_samples <= 2^40; otherwise
+ * mst_resample_tables_bytes and mst_resample_out_samples return 0 and the launchers refuse.  One launch per call, deterministic (no
+ * atomics), a row's result does not depend on the other rows, no host synchronisation. */
+size_t mst_resample_tables_bytes(int32_t orig_freq, int32_t new_freq);
+int mst_resample_init_tables(int32_t orig_freq, int32_t new_freq, void* tables, void* stream);
+int64_t mst_resample_out_samples(int64_t n_samples, int32_t orig_freq, int32_t new_freq);
+int mst_resample_forward(const float* x, int32_t rows, int64_t n_samples, int64_t row_stride, int32_t orig_freq, int32_t new_freq,
+                         const void* tables, float* y, void* stream);
+int mst_resample_backward(const float* grad_y, int32_t rows, int64_t n_samples, int32_t orig_freq, int32_t new_freq,
+                          const void* tables, float* grad_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
  * (:127-195) and the 24-band Bark spectrum of mid/side (:62-124; STFT 32768 / hop 8192 / Hann).
