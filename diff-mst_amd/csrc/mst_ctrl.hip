@@ -23,6 +23,9 @@ namespace ctrl {
 
 typedef float f32x4 __attribute__((vector_size(16)));
 #define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+#ifndef MST_DYN_LDS  // the launch's dynamic LDS (a seam: a CPU build of this file for tests pre-defines it and hands out a static buffer)
+#define MST_DYN_LDS(T, name) extern __shared__ T name[]
+#endif
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float comp(const float4& v, int j) { return j == 0 ? v.x : (j == 1 ? v.y : (j == 2 ? v.z : v.w)); }
@@ -267,7 +270,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 // qkv (bs S, 3 d) -> P (bs, H, S, S) softmax probabilities, ctx (bs S, d).  grid (H, bs, ceil(S / 8)), 256 lanes; a wave per query row.
 __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ qkv, const uint8_t* __restrict__ mask, float* __restrict__ P,
                                                   float* __restrict__ ctx, int S, int d, int dh, float scale) {
-    extern __shared__ float sm[];
+    MST_DYN_LDS(float, sm);
     float* q = sm;
     float* k = q + S * kPitch;
     float* v = k + S * kPitch;
@@ -315,7 +318,7 @@ __global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ qkv,
 // dS = P (.) (dP - rowsum(dP (.) P)) with dP = dO V^T, written unscaled.  grid (H, bs, ceil(S / 8)), 256 lanes
 __global__ __launch_bounds__(256) void k_attn_bwd1(const float* __restrict__ qkv, const float* __restrict__ dctx, const float* __restrict__ P,
                                                    float* __restrict__ dS, int S, int d, int dh) {
-    extern __shared__ float sm[];
+    MST_DYN_LDS(float, sm);
     float* v = sm;
     float* go = v + S * kPitch;
     const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd1(const float* __restrict__ qkv
 // dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO -> dqkv (bs S, 3 d).  grid (H, bs, ceil(S / 8)), 256 lanes; lane = head column
 __global__ __launch_bounds__(256) void k_attn_bwd2(const float* __restrict__ qkv, const float* __restrict__ dctx, const float* __restrict__ P,
                                                    const float* __restrict__ dS, float* __restrict__ dqkv, int S, int d, int dh, float scale) {
-    extern __shared__ float sm[];
+    MST_DYN_LDS(float, sm);
     float* q = sm;
     float* k = q + S * kPitch;
     float* go = k + S * kPitch;

@@ -191,7 +191,8 @@ class _Controller(torch.autograd.Function):
         dev = tokens.device
         desc, T = ctx.desc, ctx.T
         nt, nf, nm = ctx.heads
-        g_t = torch.zeros_like(out_t) if g_t is None else g_t.float().contiguous()
+        no_t = g_t is None  # loss on the bus heads only: the kernels want a track cotangent (zeros), the projection reports None
+        g_t = torch.zeros_like(out_t) if no_t else g_t.float().contiguous()
         g_f = None if g_f is None else g_f.float().contiguous()
         g_m = None if g_m is None else g_m.float().contiguous()
         io_g = [torch.empty_like(p) for p in io]
@@ -213,6 +214,8 @@ class _Controller(torch.autograd.Function):
                                              _layer_array(layer_g, desc.n_layers), _cabi.ptr(gtok), _cabi.ptr(ws), ctx.nbytes, st),
                        "mst_ctrl_backward")
             _hip.check(lib.mst_ctrl_tokens_backward(ctypes.byref(desc), T, _cabi.ptr(gtok), ctypes.byref(iog_s), st), "mst_ctrl_tokens_backward")
+        if no_t:
+            io_g[4] = io_g[5] = None
         return (gtok[:, :T], gtok[:, T:T + 2], None, None, *io_g, *layer_g)
 
 

@@ -141,3 +141,138 @@ def afloss(pred, target, weights, sample_rate=44100, grad=True, grad_losses=None
                                      _cabi.ptr(gx), _cabi.ptr(ws), wb, None) == 0
         out["grad_pred"] = gx
     return out
+
+
+_CTRL_LAYER_NAMES = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                     "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight",
+                     "norm2.bias")  # mst_ctrl_layer order
+_CTRL_IO_NAMES = ("track_embedding", "mix_embedding", "fx_bus_embedding", "master_bus_embedding", "track_projection.weight",
+                  "track_projection.bias", "fx_bus_projection.weight", "fx_bus_projection.bias", "master_bus_projection.weight",
+                  "master_bus_projection.bias")  # mst_ctrl_io order
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"))
+
+
+def _ctrl_setup(encoder, bs, seq):
+    """-> (desc, [(name, fp32 tensor)] layer-major in mst_ctrl_layer order, NaN workspace, its size in bytes)"""
+    from mst import _cabi
+
+    layer = encoder.layers[0]
+    d = _cabi.CtrlDesc(bs, seq, layer.self_attn.embed_dim, layer.self_attn.num_heads, layer.linear1.out_features, len(encoder.layers),
+                       float(layer.norm1.eps))
+    sd = encoder.state_dict()
+    params = [(f"layers.{l}.{n}", sd[f"layers.{l}.{n}"].detach().float().contiguous()) for l in range(len(encoder.layers))
+              for n in _CTRL_LAYER_NAMES]
+    nbytes = lib().mst_ctrl_workspace_bytes(C.byref(d))
+    assert nbytes > 0, "encoder stack outside the kernels' limits"
+    ws = _nan(nbytes // 4 + 64)  # the kernels must not rely on a cleared workspace
+    ws = ws[(-ws.data_ptr() % 256) // 4:]
+    return d, params, ws, nbytes
+
+
+def _ctrl_layer_array(tensors, n_layers):
+    from mst import _cabi
+
+    arr = (_cabi.CtrlLayer * n_layers)()
+    k = len(_cabi.CTRL_FIELDS)
+    for l in range(n_layers):
+        for j, name in enumerate(_cabi.CTRL_FIELDS):
+            setattr(arr[l], name, tensors[l * k + j].data_ptr())
+    return arr
+
+
+def _ctrl_mask(mask):
+    return None if mask is None else (mask != 0).to(torch.uint8).contiguous()
+
+
+def ctrl_stack(encoder, tokens, mask=None, grad_out=None):
+    """``mst_ctrl_forward`` / ``mst_ctrl_backward`` on a CPU ``nn.TransformerEncoder``'s weights.  tokens (bs, S, d), mask (bs, S) with
+    non-zero = padded key or None, grad_out (bs, S, d) or None (forward only) -> dict(out, grad_tokens, grads {parameter name: tensor}).
+    Every output and gradient buffer starts as NaN: an element no kernel writes fails any comparison."""
+    from mst import _cabi
+
+    L = lib()
+    bs, S, _ = tokens.shape
+    d, params, ws, nbytes = _ctrl_setup(encoder, bs, S)
+    ps = [p for _, p in params]
+    x = tokens.detach().float().contiguous()
+    m = _ctrl_mask(mask)
+    out = _nan(*x.shape)
+    rc = L.mst_ctrl_forward(C.byref(d), _cabi.ptr(x), _cabi.ptr(m), _ctrl_layer_array(ps, d.n_layers), _cabi.ptr(out), _cabi.ptr(ws), nbytes,
+                            None)
+    assert rc == 0, rc
+    res = dict(out=out)
+    if grad_out is not None:
+        g = grad_out.detach().float().contiguous()
+        grads = [_nan(*p.shape) for p in ps]
+        gx = _nan(*x.shape)
+        rc = L.mst_ctrl_backward(C.byref(d), _cabi.ptr(x), _ctrl_layer_array(ps, d.n_layers), _cabi.ptr(g),
+                                 _ctrl_layer_array(grads, d.n_layers), _cabi.ptr(gx), _cabi.ptr(ws), nbytes, None)
+        assert rc == 0, rc
+        res.update(grad_tokens=gx, grads={n: t for (n, _), t in zip(params, grads)})
+    return res
+
+
+def controller(ctrl, track_embeds, mix_embeds, mask=None, g_t=None, g_f=None, g_m=None):
+    """The whole ``TransformerController.forward`` and its backward through the C ABI (``mst_ctrl_tokens_forward``, ``mst_ctrl_forward``,
+    ``mst_ctrl_heads_forward`` and their backwards) on a CPU controller's weights.  g_t None = forward only; g_f / g_m None = no gradient
+    on that head (its projection gradients are then left as the kernels found them: NaN).
+    -> dict(out_t, out_f, out_m, mask_ext, grad_track_embeds, grad_mix_embeds, grads {parameter name: tensor})."""
+    from mst import _cabi
+
+    L = lib()
+    bs, T, D = track_embeds.shape
+    enc = ctrl.transformer_encoder
+    d, params, ws, nbytes = _ctrl_setup(enc, bs, T + 4)
+    ps = [p for _, p in params]
+    sd = ctrl.state_dict()
+    io = [sd[n].detach().float().contiguous() for n in _CTRL_IO_NAMES]
+    nt, nf, nm = io[4].shape[0], io[6].shape[0], io[8].shape[0]
+
+    def io_struct(tensors):
+        s = _cabi.CtrlIO()
+        for name, t in zip(_cabi.CTRL_IO_FIELDS, tensors):
+            setattr(s, name, t.data_ptr() if t is not None else None)
+        return s
+
+    te, me = track_embeds.detach().float().contiguous(), mix_embeds.detach().float().contiguous()
+    m_in = _ctrl_mask(mask)
+    tokens, z = _nan(bs, T + 4, D), _nan(bs, T + 4, D)
+    m_ext = torch.full((bs, T + 4), 0xAA, dtype=torch.uint8) if mask is not None else None
+    out_t, out_f, out_m = _nan(bs, T, nt), _nan(bs, nf), _nan(bs, nm)
+    io_s = io_struct(io)
+    rc = L.mst_ctrl_tokens_forward(C.byref(d), T, _cabi.ptr(te), _cabi.ptr(me), _cabi.ptr(m_in), C.byref(io_s), _cabi.ptr(tokens),
+                                   _cabi.ptr(m_ext), None)
+    assert rc == 0, rc
+    rc = L.mst_ctrl_forward(C.byref(d), _cabi.ptr(tokens), _cabi.ptr(m_ext), _ctrl_layer_array(ps, d.n_layers), _cabi.ptr(z), _cabi.ptr(ws),
+                            nbytes, None)
+    assert rc == 0, rc
+    rc = L.mst_ctrl_heads_forward(C.byref(d), T, _cabi.ptr(z), C.byref(io_s), nt, nf, nm, _cabi.ptr(out_t), _cabi.ptr(out_f), _cabi.ptr(out_m),
+                                  None)
+    assert rc == 0, rc
+    res = dict(out_t=out_t, out_f=out_f, out_m=out_m, mask_ext=m_ext, tokens=tokens, z=z)
+    if g_t is None:
+        return res
+    f32 = lambda g: None if g is None else g.detach().float().contiguous()
+    g_t, g_f, g_m = f32(g_t), f32(g_f), f32(g_m)
+    io_g = [_nan(*p.shape) for p in io]
+    layer_g = [_nan(*p.shape) for p in ps]
+    gz, gtok = _nan(*z.shape), _nan(*tokens.shape)
+    sbytes = L.mst_ctrl_heads_scratch_bytes(C.byref(d), T)
+    assert sbytes > 0
+    scratch = _nan(sbytes // 4)
+    iog_s = io_struct(io_g)
+    rc = L.mst_ctrl_heads_backward(C.byref(d), T, _cabi.ptr(z), C.byref(io_s), nt, nf, nm, _cabi.ptr(out_t), _cabi.ptr(out_f), _cabi.ptr(out_m),
+                                   _cabi.ptr(g_t), _cabi.ptr(g_f), _cabi.ptr(g_m), C.byref(iog_s), _cabi.ptr(gz), _cabi.ptr(scratch), None)
+    assert rc == 0, rc
+    rc = L.mst_ctrl_backward(C.byref(d), _cabi.ptr(tokens), _ctrl_layer_array(ps, d.n_layers), _cabi.ptr(gz),
+                             _ctrl_layer_array(layer_g, d.n_layers), _cabi.ptr(gtok), _cabi.ptr(ws), nbytes, None)
+    assert rc == 0, rc
+    rc = L.mst_ctrl_tokens_backward(C.byref(d), T, _cabi.ptr(gtok), C.byref(iog_s), None)
+    assert rc == 0, rc
+    grads = {n: g.view_as(sd[n]) for n, g in zip(_CTRL_IO_NAMES, io_g)}
+    grads.update({"transformer_encoder." + n: t for (n, _), t in zip(params, layer_g)})
+    res.update(grad_track_embeds=gtok[:, :T], grad_mix_embeds=gtok[:, T:T + 2], grad_z=gz, grads=grads)
+    return res

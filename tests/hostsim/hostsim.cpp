@@ -4,6 +4,7 @@ namespace hostsim {
 thread_local dim3 t_threadIdx, t_blockIdx, t_blockDim, t_gridDim;
 thread_local BlockCtx* t_ctx = nullptr;
 thread_local unsigned t_tid = 0;
+alignas(16) float g_dyn_lds[kDynLdsBytes / sizeof(float)];
 }  // namespace hostsim
 
 // The spectrogram encoder (mst_cnn*.hip: bf16 MFMA kernels) is not built into the simulator library; its C-ABI entry points
@@ -18,13 +19,4 @@ int mst_cnn14_forward(const mst_cnn14_desc*, const float*, const mst_cnn14_param
 int mst_cnn14_backward(const mst_cnn14_desc*, const float*, const mst_cnn14_params*, const float*, const mst_cnn14_grads*, void*, size_t, void*) { return 801; }
 int mst_cnn14_forward_sync(const mst_cnn14_desc*, const float*, const mst_cnn14_params*, float*, float*, void*, size_t, void*, mst_sync_fn, void*) { return 801; }
 int mst_cnn14_backward_sync(const mst_cnn14_desc*, const float*, const mst_cnn14_params*, const float*, const mst_cnn14_grads*, void*, size_t, void*, mst_sync_fn, void*) { return 801; }
-// the controller's encoder stack (fp32 matrix-core kernels) is GPU-only as well
-size_t mst_ctrl_workspace_bytes(const mst_ctrl_desc*) { return 0; }
-int mst_ctrl_forward(const mst_ctrl_desc*, const float*, const uint8_t*, const mst_ctrl_layer*, float*, void*, size_t, void*) { return 801; }
-int mst_ctrl_backward(const mst_ctrl_desc*, const float*, const mst_ctrl_layer*, const float*, const mst_ctrl_layer_grads*, float*, void*, size_t, void*) { return 801; }
-int mst_ctrl_tokens_forward(const mst_ctrl_desc*, int32_t, const float*, const float*, const uint8_t*, const mst_ctrl_io*, float*, uint8_t*, void*) { return 801; }
-int mst_ctrl_heads_forward(const mst_ctrl_desc*, int32_t, const float*, const mst_ctrl_io*, int32_t, int32_t, int32_t, float*, float*, float*, void*) { return 801; }
-size_t mst_ctrl_heads_scratch_bytes(const mst_ctrl_desc*, int32_t) { return 0; }
-int mst_ctrl_heads_backward(const mst_ctrl_desc*, int32_t, const float*, const mst_ctrl_io*, int32_t, int32_t, int32_t, const float*, const float*, const float*, const float*, const float*, const float*, const mst_ctrl_io_grads*, float*, void*, void*) { return 801; }
-int mst_ctrl_tokens_backward(const mst_ctrl_desc*, int32_t, const float*, const mst_ctrl_io_grads*, void*) { return 801; }
 }

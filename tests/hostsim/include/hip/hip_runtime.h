@@ -61,8 +61,18 @@ static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e =
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return 0; }
 static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
+// the per-kernel dynamic-LDS cap: nothing to raise here (the buffer below is always whole)
+enum { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
+static inline hipError_t hipFuncSetAttribute(const void*, int, int) { return 0; }
+// device code calls the global min / max of the HIP headers
+static inline int min(int a, int b) { return b < a ? b : a; }
+static inline int max(int a, int b) { return a < b ? b : a; }
 
 namespace hostsim {
+// dynamic LDS (`extern __shared__`): one static buffer of the gfx950 LDS size, shared by every launch - blocks run one after
+// another.  Kernel sources declare theirs through MST_DYN_LDS, which expands to `extern __shared__ T name[]` under hipcc.
+constexpr size_t kDynLdsBytes = 160 * 1024;
+extern float g_dyn_lds[kDynLdsBytes / sizeof(float)];
 struct BlockCtx {
     unsigned nthreads = 0;
     std::unique_ptr<std::barrier<>> block_bar;
@@ -128,6 +138,7 @@ void launch(K kernel, dim3 grid, dim3 block, Args... args) {
 #define blockDim (hostsim::t_blockDim)
 #define gridDim (hostsim::t_gridDim)
 
+#define MST_DYN_LDS(T, name) T* const name = reinterpret_cast<T*>(hostsim::g_dyn_lds)
 #define HIP_KERNEL_NAME(...) __VA_ARGS__
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
     hostsim::launch(kernel, dim3(grid), dim3(block), ##__VA_ARGS__)
@@ -136,6 +147,7 @@ static inline void __syncthreads() { hostsim::t_ctx->block_bar->arrive_and_wait(
 // wave-scope fence / barrier: the simulator's lanes are OS threads, so "the wave runs in lockstep" has to be a real rendezvous
 static inline void __builtin_amdgcn_wave_barrier() { hostsim::t_ctx->wave_bar[hostsim::t_tid >> 6]->arrive_and_wait(); }
 #define __builtin_amdgcn_fence(order, ...) __atomic_thread_fence(order)
+static inline void __builtin_amdgcn_s_waitcnt(int) {}  // memory of the simulated lanes is coherent at every rendezvous
 static inline void __builtin_amdgcn_s_barrier() { hostsim::t_ctx->block_bar->arrive_and_wait(); }
 template <typename T> inline T __shfl(T v, int src, int = 64) { return hostsim::shfl_idx(v, (unsigned)src); }
 template <typename T> inline T __shfl_xor(T v, int m, int = 64) { return hostsim::shfl_idx(v, (hostsim::t_tid & 63u) ^ (unsigned)m); }
@@ -250,6 +262,7 @@ static inline float __builtin_amdgcn_fmed3f(float a, float b, float c) { return 
 static inline float __builtin_amdgcn_sqrtf(float x) { return sqrtf(x); }
 static inline float __builtin_amdgcn_rsqf(float x) { return 1.0f / sqrtf(x); }
 static inline float __fdividef(float a, float b) { return a / b; }
+#define __expf(x) expf(x)  // a macro: glibc's <math.h> already declares a function of this name
 static inline long long __double_as_longlong(double d) { long long v; memcpy(&v, &d, 8); return v; }
 static inline double __longlong_as_double(long long v) { double d; memcpy(&d, &v, 8); return d; }
 static inline float __int_as_float(int v) { float f; memcpy(&f, &v, 4); return f; }
