@@ -444,11 +444,12 @@ __global__ __launch_bounds__(kEqWG) void k_eq_zs_mfma(const float* __restrict__ 
         for (int dd = 0; dd < kStates; ++dd) agg[((int64_t)sig * kStates + dd) * kMaxTiles1 + wt] = st[dd];
     }
 }
-void launch_eq_zs_mfma(int dir, const float* in, int64_t in_stride, const float* wz, int split, float* z, int nc_pad, int64_t n, int nsig,
-                       hipStream_t stream, const float* pw1, int ntiles, float* agg) {
-    const dim3 grid(ntiles, nsig), block(kEqWG);
-    if (dir == EQ_FWD) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eq_zs_mfma<EQ_FWD>), grid, block, 0, stream, in, in_stride, wz, split, z, nc_pad, n, pw1, ntiles, agg);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eq_zs_mfma<EQ_ADJ>), grid, block, 0, stream, in, in_stride, wz, split, z, nc_pad, n, pw1, ntiles, agg);
+// pw1 of the SCAN1 kernels; null selects the generic ones
+static const float* pw1_of(const EqPass& p) { return p.eq1 ? p.pow1 : nullptr; }
+void launch_eq_zs_mfma(const EqPass& p, hipStream_t stream) {
+    const dim3 grid(p.ntiles, p.nsig), block(kEqWG);
+    if (p.dir == EQ_FWD) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eq_zs_mfma<EQ_FWD>), grid, block, 0, stream, p.in, p.in_stride, p.wz, p.split, p.z, p.nc_pad, p.n, pw1_of(p), p.ntiles, p.agg);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_eq_zs_mfma<EQ_ADJ>), grid, block, 0, stream, p.in, p.in_stride, p.wz, p.split, p.z, p.nc_pad, p.n, pw1_of(p), p.ntiles, p.agg);
 }
 
 // ---- the all-pole bank's carry scan by ONE wave, riding on the master-bus forward run (round 4) -------------------------------
@@ -575,15 +576,23 @@ __global__ __launch_bounds__(kEqWG) void k_master_run_apscan(const float* __rest
     if (fast) cascade_body<DIR, true, false, true, true, AP, ZSIN>(in, in_stride, out, out_stride, rc, 0, s0, nullptr, nc_pad, n, nullptr, 0, pw1, ntiles, agg, tile, zp, sig, bx, zi);
     else cascade_body<DIR, true, false, true, false, AP, ZSIN>(in, in_stride, out, out_stride, rc, 0, s0, nullptr, nc_pad, n, nullptr, 0, pw1, ntiles, agg, tile, zp, sig, bx, zi);
 }
-void launch_master_run_apscan(const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc, const float* s0, int nc_pad,
-                              int64_t n, int nsig, hipStream_t stream, const float* pw1, int ntiles, float* agg, float* zp,
-                              const float* sc_z, float* sc_s0, const float* sc_tab, int sc_jobs, int sc_nc, int sc_sh, int dir, const ZsIn* zi) {
-    const ApScanArgs sc{sc_z, sc_s0, sc_tab, sc_jobs, sc_nc, nc_pad, sc_sh, dir == EQ_ADJ ? 1 : 0};
-    const dim3 grid(ntiles, nsig + (sc_jobs + ntiles - 1) / ntiles), block(kEqWG);
-    const ZsIn z0 = zi ? *zi : ZsIn{};
+// ---- host-side launch helpers ----------------------------------------------------------------------
+// The run launches read the state entering every chunk: the carry-scan launch's output, or - SCAN1 kernels - the zero-state launch's
+// in-tile end states
+static const float* run_s0(const EqPass& p) { return p.eq1 ? p.z : p.s; }
+static ZsIn zs_in(const EqPass& p, bool zs_inside) { return zs_inside ? ZsIn{p.wz, p.gran, p.gran_near, p.status} : ZsIn{}; }
+void launch_master_run_apscan(const EqPass& p, bool zs_inside, hipStream_t stream) {
+    ApScanArgs sc{};
+    sc.z = p.scan.z;
+    sc.s0 = p.scan.s0;
+    sc.tab = p.scan.tab;
+    sc.jobs = p.scan.jobs; sc.nc = p.nc; sc.nc_pad = p.nc_pad; sc.sh = p.scan.sh;
+    sc.stereo = p.dir == EQ_ADJ ? 1 : 0;
+    const dim3 grid(p.ntiles, p.nsig + (sc.jobs + p.ntiles - 1) / p.ntiles), block(kEqWG);
+    const ZsIn z0 = zs_in(p, zs_inside);
 #define MST_LAUNCH_MRA(D, Z) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_master_run_apscan<D, Z>), grid, block, 0, stream, in, in_stride, out, out_stride, rc, s0, nc_pad, n, pw1, ntiles, agg, zp, nsig, sc, z0)
-    if (dir == EQ_FWD) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_master_run_apscan<D, Z>), grid, block, 0, stream, p.in, p.in_stride, p.out, p.out_stride, p.rc, run_s0(p), p.nc_pad, p.n, pw1_of(p), p.ntiles, p.agg, p.zp, p.nsig, sc, z0)
+    if (p.dir == EQ_FWD) {
         if (z0.wz) MST_LAUNCH_MRA(EQ_FWD, true);
         else MST_LAUNCH_MRA(EQ_FWD, false);
     } else {
@@ -593,65 +602,82 @@ void launch_master_run_apscan(const float* in, int64_t in_stride, float* out, in
 #undef MST_LAUNCH_MRA
 }
 
-// ---- host-side launch helpers (called from mst_console.hip) --------------------------------------
-// pw1 != nullptr selects the SCAN1 kernels (rows of ntiles <= kMaxTiles1 tiles): `z` then receives, and `s0` must be,
-// the zs launch's in-tile end states, and no carry-scan launch goes in between.
-void launch_cascade(int dir, bool run, const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc,
-                    int split, const float* s0, float* z, int nc_pad, int64_t n, int nsig, hipStream_t stream, const float* pw1,
-                    int ntiles, float* agg, float* zp) {
-    const dim3 grid(pw1 ? ntiles : nc_pad / kEqWG, nsig), block(kEqWG);
+// eq1 selects the SCAN1 kernels: `z` then receives, and the run reads, the zs launch's in-tile end states
+void launch_cascade(const EqPass& p, bool run, hipStream_t stream) {
+    const float* pw1 = pw1_of(p);
+    const dim3 grid(pw1 ? p.ntiles : p.nc_pad / kEqWG, p.nsig), block(kEqWG);
     float* const nozs = nullptr;
-    if (zp && dir == EQ_FWD && run) {  // forward run + all-pole bank
-        if (pw1)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, false, true, true>), grid, block, 0, stream, in, in_stride, out,
-                               out_stride, rc, split, s0, z, nc_pad, n, nozs, 0, pw1, ntiles, agg, zp);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, false, false, true>), grid, block, 0, stream, in, in_stride, out,
-                               out_stride, rc, split, s0, z, nc_pad, n, nozs, 0, pw1, ntiles, agg, zp);
-        return;
-    }
-#define MST_LAUNCH_CASCADE(D, R, S) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<D, R, false, S>), grid, block, 0, stream, in, in_stride, out, out_stride, rc, \
-                       split, s0, z, nc_pad, n, nozs, 0, pw1, ntiles, agg, nozs)
+    float* out = run ? p.out : nullptr;
+    const int64_t out_stride = run ? p.out_stride : 0;
+    const float* s0 = run ? run_s0(p) : nullptr;
+    float* z = run ? nullptr : p.z;
+    float* zp = (run && p.dir == EQ_FWD) ? p.zp : nullptr;
+#define MST_LAUNCH_CASCADE(D, R, ...) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<D, R, false, __VA_ARGS__>), grid, block, 0, stream, p.in, p.in_stride, out, out_stride, p.rc, \
+                       p.split, s0, z, p.nc_pad, p.n, nozs, 0, pw1, p.ntiles, p.agg, zp)
+    if (zp) {  // forward run + all-pole bank
+        if (pw1) MST_LAUNCH_CASCADE(EQ_FWD, true, true, true);
+        else MST_LAUNCH_CASCADE(EQ_FWD, true, false, true);
+    } else
     if (pw1) {
-        if (dir == EQ_FWD && !run) MST_LAUNCH_CASCADE(EQ_FWD, false, true);
-        else if (dir == EQ_FWD) MST_LAUNCH_CASCADE(EQ_FWD, true, true);
+        if (p.dir == EQ_FWD && !run) MST_LAUNCH_CASCADE(EQ_FWD, false, true);
+        else if (p.dir == EQ_FWD) MST_LAUNCH_CASCADE(EQ_FWD, true, true);
         else if (!run) MST_LAUNCH_CASCADE(EQ_ADJ, false, true);
         else MST_LAUNCH_CASCADE(EQ_ADJ, true, true);
     } else {
-        if (dir == EQ_FWD && !run) MST_LAUNCH_CASCADE(EQ_FWD, false, false);
-        else if (dir == EQ_FWD) MST_LAUNCH_CASCADE(EQ_FWD, true, false);
+        if (p.dir == EQ_FWD && !run) MST_LAUNCH_CASCADE(EQ_FWD, false, false);
+        else if (p.dir == EQ_FWD) MST_LAUNCH_CASCADE(EQ_FWD, true, false);
         else if (!run) MST_LAUNCH_CASCADE(EQ_ADJ, false, false);
         else MST_LAUNCH_CASCADE(EQ_ADJ, true, false);
     }
 #undef MST_LAUNCH_CASCADE
 }
 
-void launch_cascade_run_gc(const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc, int split,
-                           const float* s0, int nc_pad, int64_t n, int nsig, float* zs_comp, int nblk_comp, hipStream_t stream,
-                           const float* pw1, int ntiles, float* agg, float* zp, const ZsIn* zi) {
+void launch_cascade_run_gc(const EqPass& p, bool zs_inside, hipStream_t stream) {
     static_assert(kWG * kCompChunk % kEqChunk == 0 && kEqWG % (kWG * kCompChunk / kEqChunk) == 0, "a compressor block must be a power-of-two group of EQ lanes");
-    const dim3 grid(pw1 ? ntiles : nc_pad / kEqWG, nsig), block(kEqWG);
-    if (zi && zi->wz && pw1) {  // zero-state pass inside the launch
-        if (zp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade_zsin<EQ_FWD, true, true>), grid, block, 0, stream, in, in_stride, out, out_stride, rc, split, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, zp, *zi);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade_zsin<EQ_FWD, true, false>), grid, block, 0, stream, in, in_stride, out, out_stride, rc, split, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, zp, *zi);
-        return;
+    const float* pw1 = pw1_of(p);
+    const dim3 grid(pw1 ? p.ntiles : p.nc_pad / kEqWG, p.nsig), block(kEqWG);
+#define MST_LAUNCH_ZSIN(AP) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade_zsin<EQ_FWD, true, AP>), grid, block, 0, stream, p.in, p.in_stride, p.out, p.out_stride, p.rc, p.split, p.nc_pad, p.n, p.zs_comp, p.nblk_comp, pw1, p.ntiles, p.zp, zs_in(p, true))
+#define MST_LAUNCH_GC(...) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, true, __VA_ARGS__>), grid, block, 0, stream, p.in, p.in_stride, p.out, p.out_stride, p.rc, p.split, run_s0(p), (float*)nullptr, p.nc_pad, p.n, p.zs_comp, p.nblk_comp, pw1, p.ntiles, p.agg, p.zp)
+    if (zs_inside) {  // zero-state pass inside the launch
+        if (p.zp) MST_LAUNCH_ZSIN(true);
+        else MST_LAUNCH_ZSIN(false);
+    } else if (p.zp) {  // + the all-pole bank
+        if (pw1) MST_LAUNCH_GC(true, true);
+        else MST_LAUNCH_GC(false, true);
+    } else {
+        if (pw1) MST_LAUNCH_GC(true);
+        else MST_LAUNCH_GC(false);
     }
-    if (zp) {
-        if (pw1)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, true, true, true>), grid, block, 0, stream, in, in_stride, out, out_stride,
-                               rc, split, s0, (float*)nullptr, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, agg, zp);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, true, false, true>), grid, block, 0, stream, in, in_stride, out, out_stride,
-                               rc, split, s0, (float*)nullptr, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, agg, zp);
-        return;
+#undef MST_LAUNCH_ZSIN
+#undef MST_LAUNCH_GC
+}
+
+// The whole EQ stage of one row family: zero-state pass -> carry scan -> run.  Three forms of the zero-state pass:
+//   inside the run launch (ZsIn, mst_kernels.h) - the runs with that variant are the gain-computer run and the master rows' run with scan jobs;
+//   eq1: its own launch on the matrix pipe, the run scans the tile aggregates itself;
+//   else: the generic kernel, then the carry-scan launch (mst_scan.hip).
+void launch_eq_pass(const EqPass& p, hipStream_t stream) {
+    const bool gc = p.zs_comp != nullptr, jobs = p.scan.jobs > 0;
+    // the gain-computer run (track rows): only while (almost) every tile of the launch is resident at once - with many rounds of workgroups
+    // (cfg #3: 32768 tiles, 8 rounds) the stand-alone zero-state launch streams the rows at the HBM rate and the merged form measured 0.6 % slower
+#ifndef MST_ZSIN_MAX_TILES
+#define MST_ZSIN_MAX_TILES 8192
+#endif
+    const bool zs_inside = p.eq1 && p.gran && (gc ? (int64_t)p.nsig * p.ntiles <= MST_ZSIN_MAX_TILES : jobs);
+    if (!zs_inside) {
+        if (p.eq1) {
+            launch_eq_zs_mfma(p, stream);
+        } else {
+            launch_cascade(p, false, stream);
+            launch_scan12(p, stream);
+        }
     }
-    if (pw1)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, true, true>), grid, block, 0, stream, in, in_stride, out, out_stride,
-                           rc, split, s0, (float*)nullptr, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, agg, (float*)nullptr);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cascade<EQ_FWD, true, true, false>), grid, block, 0, stream, in, in_stride, out, out_stride,
-                           rc, split, s0, (float*)nullptr, nc_pad, n, zs_comp, nblk_comp, pw1, ntiles, agg, (float*)nullptr);
+    if (gc) launch_cascade_run_gc(p, zs_inside, stream);  // EQ run fused with the gain computer + per-block envelope aggregates
+    else if (jobs) launch_master_run_apscan(p, zs_inside, stream);
+    else launch_cascade(p, true, stream);
 }
 
 }  // namespace mst

@@ -1,5 +1,9 @@
-// mst_kernels.h - argument blocks and host-side launch helpers shared by the console translation
-// units (each kernel is launched only from the file that defines it: no relocatable device code).
+// mst_kernels.h - what the console translation units share on the host side (each kernel is launched only from the file that
+// defines it: no relocatable device code):
+//   - the kernels' argument blocks (PrepArgs ... CompBwdArgs), passed by value and filled BY MEMBER NAME wherever they are built;
+//   - EqPass, the description of one EQ pass over one family of rows, eq_rows() / allpole_rows(), the views of the workspace layout
+//     that fill it, and launch_eq_pass(), which turns it into launches;
+//   - the launch functions of the other stages.
 #pragma once
 #include "mst_common.h"
 
@@ -86,7 +90,7 @@ void launch_basic_backward(const BasicArgs& a, hipStream_t stream);
 void launch_prep(const PrepArgs& a, hipStream_t stream);
 void launch_prep_bwd(const PrepBwdArgs& a, hipStream_t stream);
 
-// ---- mst_eq.hip
+// ---- mst_eq.hip, mst_scan.hip: the EQ stage
 // The zero-state pass of a SCAN1 run INSIDE the run launch (round 5; wz = nullptr: off - a zs launch went before).  Every tile forms
 // its zero-state chunk end states on the matrix pipe itself, publishes its 12-state aggregate as granules and picks up the aggregates
 // of the tiles before it (mst_common.h: gran_publish_vec / gran_read_vec).
@@ -96,31 +100,101 @@ struct ZsIn {
     int64_t gran_near;  // the near copies follow this many granules later
     int32_t* status;    // raised to kStatusExchangeTimeout when a wait gives up (may be null)
 };
-// zp != nullptr (forward run only): the all-pole bank of the coefficient-gradient pass rides along, its zero-state chunk
-// end states are written to zp (nsig x 24 x nc_pad) and the backward starts at the all-pole carry scan.
-// pw1 (in-wave scan tables of these rows) != nullptr: SCAN1 kernels, no carry-scan launch between zs and run (mst_eq.hip);
-// agg (nsig x 12 x kMaxTiles1) carries the tile aggregates from the zs launch to the run launch
-void launch_cascade(int dir, bool run, const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc,
-                    int split, const float* s0, float* z, int nc_pad, int64_t n, int nsig, hipStream_t stream,
-                    const float* pw1 = nullptr, int ntiles = 0, float* agg = nullptr, float* zp = nullptr);
-// forward run of mono rows fused with the compressor's zero-state block aggregates (no separate zero-state pass over the EQ output)
-void launch_cascade_run_gc(const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc, int split,
-                           const float* s0, int nc_pad, int64_t n, int nsig, float* zs_comp, int nblk_comp, hipStream_t stream,
-                           const float* pw1 = nullptr, int ntiles = 0, float* agg = nullptr, float* zp = nullptr, const ZsIn* zi = nullptr);
-// zero-state pass of the SCAN1 path on the matrix pipe: chunk end states = W^T chunk (wz: filter rows x 64 x 16, made by k_prep)
-void launch_eq_zs_mfma(int dir, const float* in, int64_t in_stride, const float* wz, int split, float* z, int nc_pad, int64_t n, int nsig,
-                       hipStream_t stream, const float* pw1, int ntiles, float* agg);
-// the master-bus forward run (SCAN1, all-pole bank riding along) with the TRACK rows' all-pole carry scan as extra one-wave
-// workgroups of the same launch (mst_eq.hip: k_master_run_apscan); sc_sh: 64 = KE 2^sc_sh
-void launch_master_run_apscan(const float* in, int64_t in_stride, float* out, int64_t out_stride, const float* rc, const float* s0, int nc_pad,
-                              int64_t n, int nsig, hipStream_t stream, const float* pw1, int ntiles, float* agg, float* zp,
-                              const float* sc_z, float* sc_s0, const float* sc_tab, int sc_jobs, int sc_nc, int sc_sh, int dir = EQ_FWD,
-                              const ZsIn* zi = nullptr);  // zi (wz != null): the master rows' zero-state pass runs inside the launch too (no k_eq_zs_mfma before it)
-
-// ---- mst_scan.hip
-void launch_scan12(bool reverse, const float* z, float* s0, const float* tab, int split, int nc, int nc_pad, int K, int nsig,
-                   hipStream_t stream);
+// The all-pole bank's chunk states of one row family: job q = two-state system (signal row q / 12, filter q % 12)
+struct ApScanJobs {
+    float* z = nullptr;    // (jobs, 2, nc_pad) zero-state chunk end states
+    float* s0 = nullptr;   // (jobs, 2, nc_pad) state entering every chunk (out of the carry scan)
+    float* tab = nullptr;  // (filter rows x 12, kPow, 4) power tables (k_prep)
+    int jobs = 0;          // 0: none
+    int sh = 0;            // 64 = K 2^sh (Layout::apscan_sh)
+};
+// One EQ pass over one family of signal rows, filled by name: zero-state pass -> carry scan -> run.  eq_rows() below fills everything
+// that lives in the workspace; the caller adds the rows that do not (the tracks, grad_tracks) and the riders it wants, and
+// launch_eq_pass() picks the launches.  A null / zero member means "not there".
+struct EqPass {
+    int dir = EQ_FWD;                // EQ_FWD: the cascade; EQ_ADJ: its adjoint (runs backwards in time)
+    // the row family
+    const float* in = nullptr;       // (nsig, in_stride)
+    float* out = nullptr;            // (nsig, out_stride)
+    int64_t in_stride = 0, out_stride = 0;
+    const float* rc = nullptr;       // row constants of the family's filter rows
+    int split = 0, nsig = 0;         // see above
+    int64_t n = 0;
+    int nc = 0, nc_pad = 0, K = 0;   // 64-sample chunks per row, padded, chunks per carry-scan lane
+    int ntiles = 0;                  // 4096-sample tiles per row
+    int eq1 = 0;                     // Layout::eq1: the carries are scanned inside the zs / run kernels (SCAN1 kernels, rows of ntiles <= kMaxTiles1
+                                     // tiles); the run then reads the zero-state launch's in-tile end states z directly and no carry-scan launch goes in between
+    // workspace arrays of this family and direction (k_prep makes the tables)
+    float* z = nullptr;              // (nsig, 12, nc_pad) zero-state chunk end states
+    float* s = nullptr;              // (nsig, 12, nc_pad) state entering every chunk: out of the carry-scan launch (eq1 = 0 only)
+    float* pow = nullptr;            // scan tables of the carry-scan launch
+    float* pow1 = nullptr;           // in-wave scan tables (eq1)
+    float* agg = nullptr;            // (nsig, 12, kMaxTiles1) tile aggregates from the zero-state launch to the run launch (eq1)
+    float* wz = nullptr;             // zero-state maps, filter rows x 64 x 16 (eq1)
+    // riders of the run launch
+    float* zs_comp = nullptr;        // forward run of mono rows: + the gain computer and the compressor's zero-state block aggregates
+    int nblk_comp = 0;               //   (nsig, nblk_comp): no separate zero-state pass over the EQ output
+    float* zp = nullptr;             // forward run: + the all-pole bank of the coefficient-gradient pass, its zero-state chunk end states
+                                     //   go to zp (nsig, 24, nc_pad) and the backward starts at the all-pole carry scan
+    ApScanJobs scan;                 // master rows: + all-pole carry scans as extra one-wave workgroups (mst_eq.hip: k_master_run_apscan)
+    // + the zero-state pass itself (round 5, ZsIn above): the tile aggregates travel as granules
+    gran_t* gran = nullptr;          // (nsig, kMaxTiles1, 12) zeroed granules; null: this family and direction has none
+    int64_t gran_near = 0;
+    int32_t* status = nullptr;       // raised to kStatusExchangeTimeout when a wait gives up (may be null)
+};
+// zero-state pass, carry scan and run of p: the only place that knows the forms these take (mst_eq.hip)
+void launch_eq_pass(const EqPass& p, hipStream_t stream);
+// the single launches behind it.  launch_cascade: the generic kernel, zero-state pass (run = false: out, zp unused) or run
+void launch_cascade(const EqPass& p, bool run, hipStream_t stream);
+void launch_cascade_run_gc(const EqPass& p, bool zs_inside, hipStream_t stream);     // run + zs_comp rider
+void launch_master_run_apscan(const EqPass& p, bool zs_inside, hipStream_t stream);  // run + scan rider; sh: 64 = K 2^sh
+// zero-state pass of the SCAN1 path on the matrix pipe: chunk end states = W^T chunk
+void launch_eq_zs_mfma(const EqPass& p, hipStream_t stream);
+void launch_scan12(const EqPass& p, hipStream_t stream);  // z -> s
 void launch_scan2(const float* z, float* s0, const float* tab, int split, int nc, int nc_pad, int K, int nsig, hipStream_t stream);
+
+// The EQ stage's view of the workspace: the arrays of one row family (EQ_TRACKS: the R mono track rows; EQ_MASTER: the L/R rows of
+// the bs stereo buses) in one direction.  in / out are the family's workspace signals: forward bus -> v_m and (tracks) -> u_t,
+// adjoint du_m -> dbus and du_t -> (grad_tracks).
+enum { EQ_TRACKS = 0, EQ_MASTER = 1 };
+inline ApScanJobs allpole_rows(const Layout& L, float* ws, int family) {
+    ApScanJobs j;
+    const bool m = family == EQ_MASTER;
+    j.z = ws + (m ? L.zP_m : L.zP_t);
+    j.s0 = ws + (m ? L.sP_m : L.sP_t);
+    j.tab = ws + (m ? L.powP_m : L.powP_t);
+    j.jobs = (m ? 2 * L.bs : L.R) * 12;
+    j.sh = L.apscan_sh;
+    return j;
+}
+inline EqPass eq_rows(const Layout& L, float* ws, int family, int dir) {
+    struct Off { int64_t rc, in, out, z, s, pow, pow1, agg, wz, gran, gran_near; };
+    const int64_t none = -1, eqg_m = 2 * ((int64_t)L.R * kMaxTiles1 * kStates);  // granules are two floats wide; the master rows' follow the track rows'
+    const Off o = family == EQ_TRACKS
+        ? (dir == EQ_FWD ? Off{L.rc_t, none, L.u_t, L.zE_t, L.sE_t, L.powF_t, L.pow1F_t, L.aggF_t, L.wzF_t, L.eqg_f, L.eqg_nf}
+                         : Off{L.rc_t, L.du_t, none, L.zA_t, L.sA_t, L.powA_t, L.pow1A_t, L.aggA_t, L.wzA_t, none, 0})
+        : (dir == EQ_FWD ? Off{L.rc_m, L.bus, L.v_m, L.zE_m, L.sE_m, L.powF_m, L.pow1F_m, L.aggF_m, L.wzF_m, L.eqg_f + eqg_m, L.eqg_nf}
+                         : Off{L.rc_m, L.du_m, L.dbus, L.zA_m, L.sA_m, L.powA_m, L.pow1A_m, L.aggA_m, L.wzA_m, L.eqg_b, L.eqg_nb});
+    EqPass p;
+    p.dir = dir;
+    if (o.in != none) p.in = ws + o.in;
+    if (o.out != none) p.out = ws + o.out;
+    p.in_stride = p.out_stride = row_stride(L.N);
+    p.rc = ws + o.rc;
+    p.split = family == EQ_TRACKS ? L.R : 0;
+    p.nsig = family == EQ_TRACKS ? L.R : 2 * L.bs;
+    p.n = L.N;
+    p.nc = L.ncE; p.nc_pad = L.ncE_pad; p.K = L.KE;
+    p.ntiles = L.ntE;
+    p.eq1 = L.eq1;
+    p.z = ws + o.z; p.s = ws + o.s;
+    p.pow = ws + o.pow; p.pow1 = ws + o.pow1;
+    p.agg = ws + o.agg;
+    p.wz = ws + o.wz;
+    if (o.gran != none) p.gran = (gran_t*)(ws + o.gran);
+    p.gran_near = o.gran_near;
+    return p;
+}
 
 // ---- mst_comp.hip
 struct TrackApplyArgs {

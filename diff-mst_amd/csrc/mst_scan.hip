@@ -257,10 +257,9 @@ static void launch_scan_k(dim3 grid, hipStream_t stream, const float* z, float* 
     else if (K == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan<D, REV, 8>), grid, block, 0, stream, z, s0, tab, sub, split, nc, nc_pad, K);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan<D, REV, 0>), grid, block, 0, stream, z, s0, tab, sub, split, nc, nc_pad, K);
 }
-void launch_scan12(bool reverse, const float* z, float* s0, const float* tab, int split, int nc, int nc_pad, int K, int nsig,
-                   hipStream_t stream) {
-    if (reverse) launch_scan_k<12, true>(dim3(nsig), stream, z, s0, tab, 1, split, nc, nc_pad, K);
-    else launch_scan_k<12, false>(dim3(nsig), stream, z, s0, tab, 1, split, nc, nc_pad, K);
+void launch_scan12(const EqPass& p, hipStream_t stream) {  // the adjoint cascade's carries run from the last chunk to the first
+    if (p.dir == EQ_ADJ) launch_scan_k<12, true>(dim3(p.nsig), stream, p.z, p.s, p.pow, 1, p.split, p.nc, p.nc_pad, p.K);
+    else launch_scan_k<12, false>(dim3(p.nsig), stream, p.z, p.s, p.pow, 1, p.split, p.nc, p.nc_pad, p.K);
 }
 void launch_scan2(const float* z, float* s0, const float* tab, int split, int nc, int nc_pad, int K, int nsig, hipStream_t stream) {
     launch_scan_k<2, false>(dim3(nsig * 12), stream, z, s0, tab, 12, split, nc, nc_pad, K);

@@ -1,6 +1,7 @@
 // mst_stft.h - argument blocks shared by the two translation units of the spectrogram loss:
-//   mst_stft.hip   C ABI, tables, loss reduction, the round-1 radix-4 LDS transform kernels (any power-of-two n_fft,
-//                  any hop / window length - the generic path)
+//   mst_stft.hip   C ABI (the plan of a call, stft_args() = the one place a StftArgs is filled from it, the launch sequences), tables,
+//                  loss reduction, the round-1 radix-4 LDS transform kernels with their own in-file transform (any power-of-two
+//                  n_fft, any hop / window length - the generic path)
 //   mst_stft2.hip  the round-2 kernels on the register-radix engine (mst_fft2.h) for the reference's shape of
 //                  resolution (n_fft in {512, 2048, 8192}, hop = n_fft / 2, full-length window); compiled with
 //                  -fno-slp-vectorize (packed-fp32 pairing costs this code 40 % more registers and 60 v_mov per frame)

@@ -731,6 +731,31 @@ extern "C" int mst_mrstft_init_tables(const mst_mrstft_desc* d, void* tables, vo
     return (int)hipGetLastError();
 }
 
+// The argument block of resolution i as every transform launch takes it: inputs, tables, the resolution, its partial sums and kept
+// planes (where the plan has them).  With grad_pred (the backward): + the row sums / backward coefficients and the cotangents.
+static StftArgs stft_args(const Plan& p, const mst_mrstft_desc* d, int i, const float* pred, const float* target, const void* tables, float* ws,
+                          const float* grad_loss = nullptr, float* grad_pred = nullptr) {
+    StftArgs a{};
+    a.pred = pred;
+    a.target = target;
+    a.tables = (const float*)tables;
+    a.r = p.res[i];
+    a.log2n = p.log2n[i];
+    a.n = d->n_samples;
+    a.eps = d->eps;
+    a.ymag = p.ymag_off[i] >= 0 ? ws + p.ymag_off[i] : nullptr;
+    a.xspec = p.xspec_off[i] >= 0 ? ws + p.xspec_off[i] : nullptr;
+    if (grad_pred) {
+        a.sums = ws + p.sums_off + (int64_t)i * d->rows * 4;
+        a.coef = ws + p.coef_off + (int64_t)i * d->rows * 4;
+        a.grad_loss = grad_loss;
+        a.grad_pred = grad_pred;
+    } else {
+        a.part = ws + p.part_off[i];
+    }
+    return a;
+}
+
 // stages: 1 = transforms + row sums (+ totals when asked for), 2 = loss + backward coefficients
 static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables, float* loss,
                                  double* totals, const double* gtotals, int world, int stages, void* workspace,
@@ -779,17 +804,7 @@ static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, co
         Stft3Args q{};
         for (int w = 0; w < 3; ++w) {
             const int i = role[w];
-            StftArgs& a = q.a[w];
-            a.pred = pred;
-            a.target = target;
-            a.tables = (const float*)tables;
-            a.part = ws + p.part_off[i];
-            a.r = p.res[i];
-            a.log2n = p.log2n[i];
-            a.n = d->n_samples;
-            a.eps = d->eps;
-            a.ymag = p.ymag_off[i] >= 0 ? ws + p.ymag_off[i] : nullptr;
-            a.xspec = p.xspec_off[i] >= 0 ? ws + p.xspec_off[i] : nullptr;
+            q.a[w] = stft_args(p, d, i, pred, target, tables, ws);
             q.groups[w] = p.n_groups[i];
         }
         q.rows = d->rows;
@@ -801,17 +816,7 @@ static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, co
     }
     for (int i = 0; i < d->n_res; ++i) {
         if (!(stages & 1) || fuse3) continue;
-        StftArgs a{};
-        a.pred = pred;
-        a.target = target;
-        a.tables = (const float*)tables;
-        a.part = ws + p.part_off[i];
-        a.r = p.res[i];
-        a.log2n = p.log2n[i];
-        a.n = d->n_samples;
-        a.eps = d->eps;
-        a.ymag = p.ymag_off[i] >= 0 ? ws + p.ymag_off[i] : nullptr;
-        a.xspec = p.xspec_off[i] >= 0 ? ws + p.xspec_off[i] : nullptr;
+        StftArgs a = stft_args(p, d, i, pred, target, tables, ws);
         if (fuse && i == 0) a.tickets = reinterpret_cast<unsigned*>(ws + p.tick_off);
         const dim3 grid(p.n_groups[i], d->rows);
 #define MST_LAUNCH_FWD(NF) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stft_fwd<NF>), grid, dim3(stft_threads(NF)), 0, stream, a)
@@ -879,60 +884,44 @@ extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, 
         }
         const bool fuse2 = i512 >= 0 && i2048 >= 0 && stft2_bwd_can_fuse(d->n_samples);
         StftArgs held{};  // the 512-point launch's arguments, kept until the 2048-point resolution comes up
-        for (int pass = 0; pass < 2; ++pass) {
-            for (int k = 0; k < d->n_res; ++k) {
-                // fused pair: the 512-point resolution is visited first whatever the caller's order (it owns the samples first)
-                const int i = (fuse2 && pass == 1) ? (k == (i512 < i2048 ? i512 : i2048) ? i512 : (k == (i512 < i2048 ? i2048 : i512) ? i2048 : k)) : k;
-                if (stft2_bwd_needs_zero(p.res[i].n_fft) != (pass == 0)) continue;
-                StftArgs a{};
-                a.pred = pred;
-                a.target = target;
-                a.tables = (const float*)tables;
-                a.sums = ws + p.sums_off + (int64_t)i * d->rows * 4;
-                a.coef = ws + p.coef_off + (int64_t)i * d->rows * 4;
-                a.grad_loss = grad_loss;
-                a.grad_pred = grad_pred;
-                a.r = p.res[i];
-                a.log2n = p.log2n[i];
-                a.n = d->n_samples;
-                a.eps = d->eps;
-                a.ymag = ws + p.ymag_off[i];
-                a.xspec = p.xspec_off[i] >= 0 ? ws + p.xspec_off[i] : nullptr;
-                a.accumulate = (pass == 1 && written) ? 1 : 0;
-                if (handover && (pass == 0 || pending)) {
-                    const ResInfo& sr = p.res[p.seam_res];
-                    a.seam = ws + p.seam_off;
-                    a.seam_frames = sr.n_frames;
-                    a.seam_groups = stft2_bwd_groups(sr.n_fft, sr.n_frames, d->rows);
-                    a.seam_hop = sr.n_fft / 2;
-                    if (pass == 1) pending = false;
-                }
-                if (fuse2 && i == i512) {
-                    held = a;  // launched together with the 2048-point resolution below
-                } else if (fuse2 && i == i2048) {
-                    launch_stft2_bwd_512_2048(held, a, d->rows, stream);
-                } else {
-                    launch_stft2_bwd(a, stft2_bwd_groups(a.r.n_fft, a.r.n_frames, d->rows), d->rows, stream);
-                }
-                written = true;
+        // Visiting order: the seam-mode resolutions first, then the halo-mode ones, each group in the caller's order - except that a fused
+        // pair trades places where needed so that the 512-point resolution comes before the 2048-point one (it owns the samples first)
+        int order[kMaxRes], n_seam = 0, n_order = 0;
+        for (int i = 0; i < d->n_res; ++i)
+            if (stft2_bwd_needs_zero(p.res[i].n_fft)) order[n_order++] = i;
+        n_seam = n_order;
+        for (int i = 0; i < d->n_res; ++i)
+            if (!stft2_bwd_needs_zero(p.res[i].n_fft)) order[n_order++] = i;
+        if (fuse2 && i2048 < i512)
+            for (int k = n_seam; k < n_order; ++k) order[k] = order[k] == i512 ? i2048 : (order[k] == i2048 ? i512 : order[k]);
+        for (int k = 0; k < n_order; ++k) {
+            const int i = order[k];
+            const bool halo = k >= n_seam;
+            StftArgs a = stft_args(p, d, i, pred, target, tables, ws, grad_loss, grad_pred);
+            a.accumulate = (halo && written) ? 1 : 0;
+            if (handover && (!halo || pending)) {
+                const ResInfo& sr = p.res[p.seam_res];
+                a.seam = ws + p.seam_off;
+                a.seam_frames = sr.n_frames;
+                a.seam_groups = stft2_bwd_groups(sr.n_fft, sr.n_frames, d->rows);
+                a.seam_hop = sr.n_fft / 2;
+                if (halo) pending = false;
             }
+            if (fuse2 && i == i512) {
+                held = a;  // launched together with the 2048-point resolution below
+            } else if (fuse2 && i == i2048) {
+                launch_stft2_bwd_512_2048(held, a, d->rows, stream);
+            } else {
+                launch_stft2_bwd(a, stft2_bwd_groups(a.r.n_fft, a.r.n_frames, d->rows), d->rows, stream);
+            }
+            written = true;
         }
         return (int)hipGetLastError();
     }
     (void)hipMemsetAsync(grad_pred, 0, (size_t)d->rows * d->n_samples * sizeof(float), stream);
     for (int i = 0; i < d->n_res; ++i) {
-        StftArgs a{};
-        a.pred = pred;
-        a.target = target;
-        a.tables = (const float*)tables;
-        a.sums = ws + p.sums_off + (int64_t)i * d->rows * 4;
-        a.coef = ws + p.coef_off + (int64_t)i * d->rows * 4;
-        a.grad_loss = grad_loss;
-        a.grad_pred = grad_pred;
-        a.r = p.res[i];
-        a.log2n = p.log2n[i];
-        a.n = d->n_samples;
-        a.eps = d->eps;
+        StftArgs a = stft_args(p, d, i, pred, target, tables, ws, grad_loss, grad_pred);
+        a.ymag = a.xspec = nullptr;  // the generic kernels recompute the transforms: no kept planes
         // three LDS buffers (pairing two frames per inverse FFT) fit up to n_fft = 4096; 8192 runs one frame per workgroup
         const bool pair = a.r.n_fft <= 4096;
         const dim3 grid(pair ? (a.r.n_frames + 1) / 2 : a.r.n_frames, d->rows);

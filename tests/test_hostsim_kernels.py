@@ -20,7 +20,17 @@ def ranges():
     return oc.param_ranges(44100)
 
 
-def test_console_forward_backward_small(ranges):
+# stages switched off next to FULL: the branches of the launch chain that a call with every stage on does not take
+SMALL_CASES = {
+    "full": {},
+    "no_track_compressor": dict(use_track_compressor=False),  # the plain track run
+    "no_master_bus": dict(use_master_bus=False),  # output fader only, on the apply and on the adjoint
+    "no_master_bus_no_output_fader": dict(use_master_bus=False, use_output_fader=False),  # the bus is the mix, cp_m cleared by memset
+}
+_small_calls = {}
+
+
+def small_draw():
     torch.manual_seed(1)
     bs, T, n = 1, 2, 5003  # ragged: not a multiple of 4, 8 or 64; longer than both look-aheads
     tracks = 0.1 * torch.randn(bs, T, n)
@@ -29,18 +39,52 @@ def test_console_forward_backward_small(ranges):
     tp[..., 21] *= 0.2
     mp[..., 20] *= 0.2
     gmix, gmixed = torch.randn(bs, 2, n), torch.randn(bs, 2, T, n)
-    out = harness.console(ranges, tracks, tp, fp, mp, FULL, grad_mix=gmix, grad_mixed=gmixed, want_grad_tracks=True)
+    return tracks, tp, fp, mp, gmix, gmixed
+
+
+def small_call(ranges, case):
+    """The saving call of one case, made once per session (a simulator call of this size takes 10-20 s)."""
+    if case not in _small_calls:
+        tracks, tp, fp, mp, gmix, gmixed = small_draw()
+        _small_calls[case] = harness.console(ranges, tracks, tp, fp, mp, dict(FULL, **SMALL_CASES[case]), grad_mix=gmix,
+                                             grad_mixed=gmixed, want_grad_tracks=True)
+    return _small_calls[case]
+
+
+@pytest.mark.parametrize("case", list(SMALL_CASES))
+def test_console_forward_backward_small(ranges, case):
+    flags = dict(FULL, **SMALL_CASES[case])
+    tracks, tp, fp, mp, gmix, gmixed = small_draw()
+    out = small_call(ranges, case)
     assert out["status"] == 0
     tr = tracks.double().requires_grad_(True)
     a, b = tp.double().requires_grad_(True), mp.double().requires_grad_(True)
-    mixed, mix, *_ = oc.console_forward(tr, a, fp.double(), b, **FULL)
+    mixed, mix, *_ = oc.console_forward(tr, a, fp.double(), b, **flags)
     ((mix * gmix.double()).sum() + (mixed * gmixed.double()).sum()).backward()
-    _, truth, *_ = oc.console_forward(tracks.double(), tp.double(), fp.double(), mp.double(), time_domain=True, **FULL)
-    assert rel(out["mix"], truth) < 1e-4
-    assert rel(out["mixed"], mixed) < 1e-3
-    assert rel(out["grad_tracks"], tr.grad) < 1e-2
-    assert rel(out["grad_tp"], a.grad) < 2e-2
-    assert rel(out["grad_mp"], b.grad) < 2e-2
+    _, truth, *_ = oc.console_forward(tracks.double(), tp.double(), fp.double(), mp.double(), time_domain=True, **flags)
+    g_mp = torch.zeros_like(b) if b.grad is None else b.grad
+    errs = dict(mix=rel(out["mix"], truth), mixed=rel(out["mixed"], mixed), grad_tracks=rel(out["grad_tracks"], tr.grad),
+                grad_tp=rel(out["grad_tp"], a.grad))
+    if float(g_mp.abs().max()) == 0.0:  # the parameters of switched-off stages get exactly zero gradient
+        assert float(out["grad_mp"].abs().max()) == 0.0
+    else:
+        errs["grad_mp"] = rel(out["grad_mp"], g_mp)
+    print(case, {k: f"{v:.2e}" for k, v in errs.items()})
+    assert errs["mix"] < 1e-4
+    assert errs["mixed"] < 1e-3
+    assert errs["grad_tracks"] < 1e-2
+    assert errs["grad_tp"] < 2e-2
+    assert errs.get("grad_mp", 0.0) < 2e-2
+
+
+def test_console_forward_only_small(ranges):
+    """A call that saves nothing for a backward (the all-pole bank does not ride on the EQ runs, no gain planes are written) gives the
+    saving call's mix bit for bit."""
+    tracks, tp, fp, mp, _, _ = small_draw()
+    out = harness.console(ranges, tracks, tp, fp, mp, FULL)
+    assert out["status"] == 0
+    assert torch.equal(out["mix"], small_call(ranges, "full")["mix"])
+    assert torch.equal(out["mixed"], small_call(ranges, "full")["mixed"])
 
 
 def test_console_inwave_scan_eq_matches_three_kernel_eq(ranges):
