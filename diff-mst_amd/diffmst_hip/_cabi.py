@@ -118,82 +118,122 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
     _fields_ = [(name, C.c_void_p) for name in CTRL_FIELDS]
 
 
-_P = C.c_void_p
+def ptr(t):
+    """Address of a tensor (device memory, or host memory in the simulator tests) as a ``c_void_p``; NULL for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class DevPtr:
+    """Argument type of a buffer pointer: ``ptr()`` applied by ``ctypes`` at the call.  A tensor is passed as it is and goes in as
+    its ``data_ptr()``, ``None`` as NULL; an int or a ``c_void_p`` passes as ``c_void_p`` takes it and anything else is a
+    ``ctypes.ArgumentError`` - ``str`` and ``bytes`` too, which ``c_void_p`` itself would pass as the address of their characters.
+    Dtype, contiguity and device are the caller's to check (``_hip.require_cuda``, ``.float().contiguous()``)."""
+
+    @classmethod
+    def from_param(cls, obj):
+        if obj is None or hasattr(obj, "data_ptr"):
+            return ptr(obj)
+        if isinstance(obj, (str, bytes)):
+            raise TypeError("a buffer argument is a tensor, None, an address or a c_void_p")
+        return C.c_void_p.from_param(obj)
+
+
+class STATUS:
+    """Return-type marker of the entries that report a ``hipError_t``-like int (0 = ok): the launchers and the ``*_init_tables``
+    functions.  ``bind()`` makes a non-zero value of these an ``AbiError``; the sizes and counts (``c_int32`` is ``c_int`` here, so the
+    type cannot tell them apart) and ``mst_abi_version`` come back as numbers."""
+
+
+class AbiError(RuntimeError):
+    """A ``STATUS`` entry returned non-zero: ``name`` is the exported symbol that was called, ``code`` what it returned."""
+
+    def __init__(self, name, code):
+        super().__init__(f"{name} failed with hipError {code}")
+        self.name, self.code = name, code
+
+
+_P = DevPtr      # buffers
+_S = C.c_void_p  # streams, events and the sync hook's `user` pointer: raw handles
+
 
 SIGNATURES = {
     "mst_abi_version": (C.c_int, []),
     "mst_console_workspace_bytes": (C.c_size_t, [C.POINTER(ConsoleDesc)]),
     "mst_console_fx_tables_bytes": (C.c_size_t, []),
-    "mst_console_fx_init_tables": (C.c_int, [_P, _P]),
-    "mst_console_forward": (C.c_int, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, C.c_size_t, _P]),
-    "mst_console_forward_mirrored": (C.c_int, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, C.c_size_t, _P, _P, _P]),
-    "mst_console_backward": (C.c_int, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, _P, _P, _P, _P,
-                                       C.c_size_t, _P]),
-    "mst_console_backward_prepare": (C.c_int, [C.POINTER(ConsoleDesc), _P, C.c_size_t, _P]),
-    "mst_console_forward_overlapped": (C.c_int, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, C.c_size_t, _P,
-                                                 C.POINTER(ConsoleOverlap)]),
-    "mst_console_backward_overlapped": (C.c_int, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, _P, _P, _P, _P,
-                                                  C.c_size_t, _P, C.POINTER(ConsoleOverlap)]),
+    "mst_console_fx_init_tables": (STATUS, [_P, _S]),
+    "mst_console_forward": (STATUS, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_console_forward_mirrored": (STATUS, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, C.c_size_t, _S, _P, _S]),
+    "mst_console_backward": (STATUS, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, _P, _P, _P, _P,
+                                     C.c_size_t, _S]),
+    "mst_console_backward_prepare": (STATUS, [C.POINTER(ConsoleDesc), _P, C.c_size_t, _S]),
+    "mst_console_forward_overlapped": (STATUS, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, C.c_size_t, _S,
+                                               C.POINTER(ConsoleOverlap)]),
+    "mst_console_backward_overlapped": (STATUS, [C.POINTER(ConsoleDesc), _P, _P, _P, _P, C.POINTER(ConsoleFx), _P, _P, _P, _P, _P, _P, _P, _P,
+                                                C.c_size_t, _S, C.POINTER(ConsoleOverlap)]),
     "mst_mrstft_tables_bytes": (C.c_size_t, [C.POINTER(MrstftDesc)]),
-    "mst_mrstft_init_tables": (C.c_int, [C.POINTER(MrstftDesc), _P, _P]),
+    "mst_mrstft_init_tables": (STATUS, [C.POINTER(MrstftDesc), _P, _S]),
     "mst_mrstft_workspace_bytes": (C.c_size_t, [C.POINTER(MrstftDesc)]),
-    "mst_mrstft_forward": (C.c_int, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "mst_mrstft_forward_eval": (C.c_int, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "mst_mrstft_forward_partial": (C.c_int, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _P]),
-    "mst_mrstft_forward_finish": (C.c_int, [C.POINTER(MrstftDesc), _P, C.c_int32, _P, _P, C.c_size_t, _P]),
-    "mst_mrstft_backward": (C.c_int, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mst_mrstft_forward": (STATUS, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_forward_eval": (STATUS, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_forward_partial": (STATUS, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_forward_finish": (STATUS, [C.POINTER(MrstftDesc), _P, C.c_int32, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_backward": (STATUS, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_peak_normalize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
-    "mst_peak_normalize_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _P]),
-    "mst_peak_normalize_backward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _P]),
+    "mst_peak_normalize_forward": (STATUS, [_P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _S]),
+    "mst_peak_normalize_backward": (STATUS, [_P, _P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _S]),
     "mst_loudness_tables_bytes": (C.c_size_t, [C.c_int32]),
-    "mst_loudness_init_tables": (C.c_int, [C.c_int32, _P, _P]),
+    "mst_loudness_init_tables": (STATUS, [C.c_int32, _P, _S]),
     "mst_loudness_num_blocks": (C.c_int32, [C.c_int64, C.c_int32]),
     "mst_loudness_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
-    "mst_loudness_integrated": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P,
-                                          C.c_size_t, _P]),
-    "mst_loudness_normalize": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float,
-                                         _P, _P]),
+    "mst_loudness_integrated": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P,
+                                        C.c_size_t, _S]),
+    "mst_loudness_normalize": (STATUS, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float,
+                                       _P, _S]),
     "mst_resample_tables_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "mst_resample_init_tables": (C.c_int, [C.c_int32, C.c_int32, _P, _P]),
+    "mst_resample_init_tables": (STATUS, [C.c_int32, C.c_int32, _P, _S]),
     "mst_resample_out_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
-    "mst_resample_forward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
-    "mst_resample_backward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mst_resample_forward": (STATUS, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _S]),
+    "mst_resample_backward": (STATUS, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
-    "mst_afloss_init_tables": (C.c_int, [_P, _P]),
+    "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
-    "mst_afloss_forward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_size_t, _P]),
+    "mst_afloss_forward": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_spectrogram_tables_bytes": (C.c_size_t, []),
-    "mst_spectrogram_init_tables": (C.c_int, [_P, _P]),
-    "mst_spectrogram_forward": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "mst_spectrogram_init_tables": (STATUS, [_P, _S]),
+    "mst_spectrogram_forward": (STATUS, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _S]),
     "mst_cnn14_workspace_bytes": (C.c_size_t, [C.POINTER(Cnn14Desc)]),
-    "mst_cnn14_forward": (C.c_int, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, _P, _P, C.c_size_t, _P]),
-    "mst_cnn14_backward": (C.c_int, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, C.POINTER(Cnn14Grads), _P, C.c_size_t, _P]),
-    "mst_cnn14_forward_sync": (C.c_int, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, _P, _P, C.c_size_t, _P, SYNC_FN, _P]),
-    "mst_cnn14_backward_sync": (C.c_int, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, C.POINTER(Cnn14Grads), _P, C.c_size_t, _P,
-                                          SYNC_FN, _P]),
-    "mst_afloss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mst_cnn14_forward": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, _P, _P, C.c_size_t, _S]),
+    "mst_cnn14_backward": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, C.POINTER(Cnn14Grads), _P, C.c_size_t, _S]),
+    "mst_cnn14_forward_sync": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, _P, _P, C.c_size_t, _S, SYNC_FN, _S]),
+    "mst_cnn14_backward_sync": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, C.POINTER(Cnn14Grads), _P, C.c_size_t, _S,
+                                        SYNC_FN, _S]),
+    "mst_afloss_backward": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_ctrl_workspace_bytes": (C.c_size_t, [C.POINTER(CtrlDesc)]),
-    "mst_ctrl_forward": (C.c_int, [C.POINTER(CtrlDesc), _P, _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _P]),
-    "mst_ctrl_backward": (C.c_int, [C.POINTER(CtrlDesc), _P, C.POINTER(CtrlLayer), _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _P]),
-    "mst_ctrl_tokens_forward": (C.c_int, [C.POINTER(CtrlDesc), C.c_int32, _P, _P, _P, C.POINTER(CtrlIO), _P, _P, _P]),
-    "mst_ctrl_heads_forward": (C.c_int, [C.POINTER(CtrlDesc), C.c_int32, _P, C.POINTER(CtrlIO), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mst_ctrl_forward": (STATUS, [C.POINTER(CtrlDesc), _P, _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),
+    "mst_ctrl_backward": (STATUS, [C.POINTER(CtrlDesc), _P, C.POINTER(CtrlLayer), _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),
+    "mst_ctrl_tokens_forward": (STATUS, [C.POINTER(CtrlDesc), C.c_int32, _P, _P, _P, C.POINTER(CtrlIO), _P, _P, _S]),
+    "mst_ctrl_heads_forward": (STATUS, [C.POINTER(CtrlDesc), C.c_int32, _P, C.POINTER(CtrlIO), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _S]),
     "mst_ctrl_heads_scratch_bytes": (C.c_size_t, [C.POINTER(CtrlDesc), C.c_int32]),
-    "mst_ctrl_heads_backward": (C.c_int, [C.POINTER(CtrlDesc), C.c_int32, _P, C.POINTER(CtrlIO), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
-                                          C.POINTER(CtrlIO), _P, _P, _P]),
-    "mst_ctrl_tokens_backward": (C.c_int, [C.POINTER(CtrlDesc), C.c_int32, _P, C.POINTER(CtrlIO), _P]),
+    "mst_ctrl_heads_backward": (STATUS, [C.POINTER(CtrlDesc), C.c_int32, _P, C.POINTER(CtrlIO), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                        C.POINTER(CtrlIO), _P, _P, _S]),
+    "mst_ctrl_tokens_backward": (STATUS, [C.POINTER(CtrlDesc), C.c_int32, _P, C.POINTER(CtrlIO), _S]),
 }
+
+
+def _raise_on_status(code, fn, _args):
+    if code:
+        raise AbiError(fn.__name__, code)
+    return code
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
-        fn.restype = res
         fn.argtypes = args
+        if res is STATUS:
+            fn.restype, fn.errcheck = C.c_int, _raise_on_status
+        else:
+            fn.restype = res
     if lib.mst_abi_version() != ABI_VERSION:
         raise RuntimeError(f"diffmst ABI mismatch: library {lib.mst_abi_version()} != binding {ABI_VERSION}")
     return lib
-
-
-def ptr(t):
-    """Device (or host, in the simulator tests) address of a tensor, or NULL for None."""
-    return None if t is None else C.c_void_p(t.data_ptr())

@@ -1,8 +1,6 @@
 """The TransformerController's encoder stack on the HIP kernels of ``csrc/mst_ctrl.hip`` (C ABI ``mst_ctrl_forward`` /
 ``mst_ctrl_backward``): one ``torch.autograd.Function`` for all layers of a ``torch.nn.TransformerEncoder`` built the way the
 reference builds it (mst/modules.py:848-854: post-norm layers, relu, dropout 0, batch_first, no final norm)."""
-import ctypes
-
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -51,8 +49,15 @@ def _desc(encoder, bs, seq, probe=False):
     d = _cabi.CtrlDesc(bs, seq, layer.self_attn.embed_dim, layer.self_attn.num_heads, layer.linear1.out_features,
                        len(encoder.layers), float(layer.norm1.eps))
     if probe:
-        return d if _hip.lib().mst_ctrl_workspace_bytes(ctypes.byref(d)) else None
+        return d if _hip.lib().mst_ctrl_workspace_bytes(d) else None
     return d
+
+
+def _mask_bytes(mask):
+    """(bs, seq) bytes, non-zero = padded key (None stays None); a bool tensor is viewed, not converted."""
+    if mask is None:
+        return None
+    return (mask if mask.dtype is torch.bool else mask != 0).contiguous().view(torch.uint8)
 
 
 def _layer_array(tensors, n_layers):
@@ -73,18 +78,14 @@ class _EncoderStack(torch.autograd.Function):
         _hip.require_same_device(dev, mask, *params)
         x = tokens.float().contiguous()
         ps = [p.detach() if (p.dtype is torch.float32 and p.is_contiguous()) else p.detach().float().contiguous() for p in params]
-        m = None  # (bs, seq) bytes, non-zero = padded key; a bool tensor is viewed, not converted
-        if mask is not None:
-            m = mask.contiguous().view(torch.uint8) if mask.dtype is torch.bool else (mask != 0).contiguous().view(torch.uint8)
-        nbytes = lib.mst_ctrl_workspace_bytes(ctypes.byref(desc))
+        m = _mask_bytes(mask)
+        nbytes = lib.mst_ctrl_workspace_bytes(desc)
         if nbytes == 0:
             raise ValueError("TransformerController: this encoder stack is outside the kernels' limits (controller.supported)")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            rc = lib.mst_ctrl_forward(ctypes.byref(desc), _cabi.ptr(x), _cabi.ptr(m), _layer_array(ps, desc.n_layers), _cabi.ptr(out),
-                                      _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev))
-        _hip.check(rc, "mst_ctrl_forward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_ctrl_forward(desc, x, m, _layer_array(ps, desc.n_layers), out, ws, nbytes, st)
         ctx.desc, ctx.nbytes = desc, nbytes
         ctx.save_for_backward(x, ws, *ps)
         return out
@@ -98,11 +99,9 @@ class _EncoderStack(torch.autograd.Function):
         g = grad_out.float().contiguous()
         grads = [torch.empty_like(p) for p in ps]
         gx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            rc = lib.mst_ctrl_backward(ctypes.byref(ctx.desc), _cabi.ptr(x), _layer_array(ps, ctx.desc.n_layers), _cabi.ptr(g),
-                                       _layer_array(grads, ctx.desc.n_layers), _cabi.ptr(gx), _cabi.ptr(ws), ctx.nbytes,
-                                       _hip.current_stream_ptr(dev))
-        _hip.check(rc, "mst_ctrl_backward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_ctrl_backward(ctx.desc, x, _layer_array(ps, ctx.desc.n_layers), g, _layer_array(grads, ctx.desc.n_layers), gx, ws,
+                                  ctx.nbytes, st)
         return (gx, None, None, *grads)
 
 
@@ -155,12 +154,10 @@ class _Controller(torch.autograd.Function):
         ps = [_f32c(p) for p in params]
         io, layers = ps[:10], ps[10:]
         nt, nf, nm = io[4].shape[0], io[6].shape[0], io[8].shape[0]
-        m_in = None
-        if mask is not None:
-            m_in = mask.contiguous().view(torch.uint8) if mask.dtype is torch.bool else (mask != 0).contiguous().view(torch.uint8)
+        m_in = _mask_bytes(mask)
         tokens = torch.empty(bs, T + 4, D, dtype=torch.float32, device=dev)
         m_ext = torch.empty(bs, T + 4, dtype=torch.uint8, device=dev) if mask is not None else None
-        nbytes = lib.mst_ctrl_workspace_bytes(ctypes.byref(desc))
+        nbytes = lib.mst_ctrl_workspace_bytes(desc)
         if nbytes == 0:
             raise ValueError("TransformerController: this encoder stack is outside the kernels' limits (controller.supported)")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -169,14 +166,10 @@ class _Controller(torch.autograd.Function):
         out_f = torch.empty(bs, nf, dtype=torch.float32, device=dev)
         out_m = torch.empty(bs, nm, dtype=torch.float32, device=dev)
         io_s = _io_struct(io)
-        st = _hip.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_ctrl_tokens_forward(ctypes.byref(desc), T, _cabi.ptr(te), _cabi.ptr(me), _cabi.ptr(m_in), ctypes.byref(io_s),
-                                                   _cabi.ptr(tokens), _cabi.ptr(m_ext), st), "mst_ctrl_tokens_forward")
-            _hip.check(lib.mst_ctrl_forward(ctypes.byref(desc), _cabi.ptr(tokens), _cabi.ptr(m_ext), _layer_array(layers, desc.n_layers),
-                                            _cabi.ptr(z), _cabi.ptr(ws), nbytes, st), "mst_ctrl_forward")
-            _hip.check(lib.mst_ctrl_heads_forward(ctypes.byref(desc), T, _cabi.ptr(z), ctypes.byref(io_s), nt, nf, nm, _cabi.ptr(out_t),
-                                                  _cabi.ptr(out_f), _cabi.ptr(out_m), st), "mst_ctrl_heads_forward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_ctrl_tokens_forward(desc, T, te, me, m_in, io_s, tokens, m_ext, st)
+            lib.mst_ctrl_forward(desc, tokens, m_ext, _layer_array(layers, desc.n_layers), z, ws, nbytes, st)
+            lib.mst_ctrl_heads_forward(desc, T, z, io_s, nt, nf, nm, out_t, out_f, out_m, st)
         ctx.desc, ctx.nbytes, ctx.T, ctx.heads = desc, nbytes, T, (nt, nf, nm)
         ctx.save_for_backward(tokens, z, ws, out_t, out_f, out_m, *ps)
         ctx.set_materialize_grads(False)  # an unused head (fx bus off) hands None down, and its projection reports None like autograd
@@ -203,17 +196,13 @@ class _Controller(torch.autograd.Function):
         layer_g = [torch.empty_like(p) for p in layers]
         gz = torch.empty_like(z)
         gtok = torch.empty_like(tokens)
-        scratch = torch.empty(lib.mst_ctrl_heads_scratch_bytes(ctypes.byref(desc), T), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(lib.mst_ctrl_heads_scratch_bytes(desc, T), dtype=torch.uint8, device=dev)
         io_s, iog_s = _io_struct(io), _io_struct(io_g)
-        st = _hip.current_stream_ptr(dev)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_ctrl_heads_backward(ctypes.byref(desc), T, _cabi.ptr(z), ctypes.byref(io_s), nt, nf, nm, _cabi.ptr(out_t),
-                                                   _cabi.ptr(out_f), _cabi.ptr(out_m), _cabi.ptr(g_t), _cabi.ptr(g_f), _cabi.ptr(g_m),
-                                                   ctypes.byref(iog_s), _cabi.ptr(gz), _cabi.ptr(scratch), st), "mst_ctrl_heads_backward")
-            _hip.check(lib.mst_ctrl_backward(ctypes.byref(desc), _cabi.ptr(tokens), _layer_array(layers, desc.n_layers), _cabi.ptr(gz),
-                                             _layer_array(layer_g, desc.n_layers), _cabi.ptr(gtok), _cabi.ptr(ws), ctx.nbytes, st),
-                       "mst_ctrl_backward")
-            _hip.check(lib.mst_ctrl_tokens_backward(ctypes.byref(desc), T, _cabi.ptr(gtok), ctypes.byref(iog_s), st), "mst_ctrl_tokens_backward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_ctrl_heads_backward(desc, T, z, io_s, nt, nf, nm, out_t, out_f, out_m, g_t, g_f, g_m, iog_s, gz, scratch, st)
+            lib.mst_ctrl_backward(desc, tokens, _layer_array(layers, desc.n_layers), gz, _layer_array(layer_g, desc.n_layers), gtok, ws,
+                                  ctx.nbytes, st)
+            lib.mst_ctrl_tokens_backward(desc, T, gtok, iog_s, st)
         if no_t:
             io_g[4] = io_g[5] = None
         return (gtok[:, :T], gtok[:, T:T + 2], None, None, *io_g, *layer_g)

@@ -32,20 +32,11 @@ def _mrstft_desc(rows, n, resolutions, w_sc, w_log_mag, w_lin_mag, sc_per_exampl
 
 def _tables(desc, resolutions, device):
     """Twiddle + window tables: depend only on (fft_size, win_length); built once per device."""
+    lib = _hip.lib()
     key = (str(device), tuple((r[0], r[2]) for r in resolutions))
-    t = _TABLE_CACHE.get(key)
-    if t is None:
-        lib = _hip.lib()
-        nbytes = lib.mst_mrstft_tables_bytes(ctypes.byref(desc))
-        if nbytes == 0:
-            raise ValueError("unsupported STFT configuration (fft sizes must be powers of two in 128..8192, "
-                             "win_length <= fft_size, n_samples > fft_size/2)")
-        t = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _hip.check(lib.mst_mrstft_init_tables(ctypes.byref(desc), _cabi.ptr(t), _hip.current_stream_ptr(device)),
-                       "mst_mrstft_init_tables")
-        _TABLE_CACHE[key] = t
-    return t
+    return _hip.device_tables(_TABLE_CACHE, key, device, lib.mst_mrstft_tables_bytes, lib.mst_mrstft_init_tables, desc,
+                              unsupported="unsupported STFT configuration (fft sizes must be powers of two in 128..8192, "
+                                          "win_length <= fft_size, n_samples > fft_size/2)")
 
 
 class _MrstftFunction(torch.autograd.Function):
@@ -70,7 +61,7 @@ class _MrstftFunction(torch.autograd.Function):
         desc = _mrstft_desc(x.shape[0], n, cfg["resolutions"], cfg["w_sc"], cfg["w_log_mag"], cfg["w_lin_mag"],
                             cfg["sc_per_example"], cfg["eps"])
         tables = _tables(desc, cfg["resolutions"], dev)
-        nbytes = lib.mst_mrstft_workspace_bytes(ctypes.byref(desc))
+        nbytes = lib.mst_mrstft_workspace_bytes(desc)
         if nbytes == 0:
             raise ValueError("unsupported STFT configuration for this input length")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -82,10 +73,8 @@ class _MrstftFunction(torch.autograd.Function):
             import torch.distributed as dist
 
             totals = torch.empty(len(cfg["resolutions"]) * 4, dtype=torch.float64, device=dev)
-            with torch.cuda.device(dev):
-                _hip.check(lib.mst_mrstft_forward_partial(ctypes.byref(desc), _cabi.ptr(x), _cabi.ptr(y), _cabi.ptr(tables),
-                                                          _cabi.ptr(totals), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev)),
-                           "mst_mrstft_forward_partial")
+            with _hip.launch_on(dev) as st:
+                lib.mst_mrstft_forward_partial(desc, x, y, tables, totals, ws, nbytes, st)
             grp = None if group is True else group
             if dist.get_backend(grp) == "gloo":  # CPU collectives: a 96-byte round trip through the host
                 host = totals.cpu()
@@ -93,16 +82,13 @@ class _MrstftFunction(torch.autograd.Function):
                 totals.copy_(host)
             else:
                 dist.all_reduce(totals, group=grp)
-            with torch.cuda.device(dev):
-                _hip.check(lib.mst_mrstft_forward_finish(ctypes.byref(desc), _cabi.ptr(totals), dist.get_world_size(grp),
-                                                         _cabi.ptr(loss), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev)),
-                           "mst_mrstft_forward_finish")
+            with _hip.launch_on(dev) as st:
+                lib.mst_mrstft_forward_finish(desc, totals, dist.get_world_size(grp), loss, ws, nbytes, st)
         else:
             # no gradient asked for (torch.no_grad(), a detached prediction): the value only - the forward then keeps no spectra
             fwd = lib.mst_mrstft_forward if want_grad else lib.mst_mrstft_forward_eval
-            with torch.cuda.device(dev):
-                _hip.check(fwd(ctypes.byref(desc), _cabi.ptr(x), _cabi.ptr(y), _cabi.ptr(tables), _cabi.ptr(loss),
-                               _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev)), "mst_mrstft_forward")
+            with _hip.launch_on(dev) as st:
+                fwd(desc, x, y, tables, loss, ws, nbytes, st)
         if want_grad:
             ctx.desc, ctx.nbytes, ctx.shape = desc, nbytes, pred.shape
             ctx.save_for_backward(x, y, tables, ws)
@@ -119,10 +105,8 @@ class _MrstftFunction(torch.autograd.Function):
         dev = x.device
         g = grad_loss.float().reshape(1).contiguous()
         gx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_mrstft_backward(ctypes.byref(ctx.desc), _cabi.ptr(x), _cabi.ptr(y), _cabi.ptr(tables), _cabi.ptr(g),
-                                               _cabi.ptr(gx), _cabi.ptr(ws), ctx.nbytes, _hip.current_stream_ptr(dev)),
-                       "mst_mrstft_backward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_mrstft_backward(ctx.desc, x, y, tables, g, gx, ws, ctx.nbytes, st)
         return gx.view(ctx.shape), None, None, None
 
 
@@ -182,23 +166,22 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
 # AudioFeatureLoss
 # ------------------------------------------------------------------------------------------------
 AF_KEYS = ("mix-rms", "mix-crest_factor", "mix-stereo_width", "mix-stereo_imbalance", "mix-barkspectrum")
-_AF_CACHE = {}
+_AF_CACHE = {}   # engine tables per (device, sample rate)
+_AF_FBANKS = {}  # the Bark filterbank beside them, same key
 
 
 def _af_constants(device, sample_rate):
     """(twiddle/window tables, Bark filterbank) on `device`; built once."""
+    lib = _hip.lib()
     key = (str(device), int(sample_rate))
-    c = _AF_CACHE.get(key)
-    if c is None:
+    tables = _hip.device_tables(_AF_CACHE, key, device, lib.mst_afloss_tables_bytes, lib.mst_afloss_init_tables)
+    fb = _AF_FBANKS.get(key)
+    if fb is None:
         from .filter import barkscale_fbanks
 
-        lib = _hip.lib()
-        tables = torch.empty(lib.mst_afloss_tables_bytes() // 4, dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _hip.check(lib.mst_afloss_init_tables(_cabi.ptr(tables), _hip.current_stream_ptr(device)), "mst_afloss_init_tables")
         fb = barkscale_fbanks(16385, 20.0, 20000.0, 24, sample_rate).contiguous().to(device)  # reference mst/loss.py:88
-        c = _AF_CACHE[key] = (tables, fb)
-    return c
+        _AF_FBANKS[key] = fb
+    return tables, fb
 
 
 class _AudioFeatureFunction(torch.autograd.Function):
@@ -219,10 +202,8 @@ class _AudioFeatureFunction(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         losses = torch.empty(5, dtype=torch.float32, device=dev)
         w = (ctypes.c_float * 5)(*[float(v) for v in weights])
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_afloss_forward(_cabi.ptr(x), _cabi.ptr(y), bs, n, w, _cabi.ptr(tables), _cabi.ptr(fb),
-                                              _cabi.ptr(losses), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev)),
-                       "mst_afloss_forward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_forward(x, y, bs, n, w, tables, fb, losses, ws, nbytes, st)
         ctx.meta = (bs, n, w, nbytes, pred.shape)
         ctx.save_for_backward(x, y, tables, fb, ws)
         # five 0-dim outputs (views of one buffer) instead of one (5,) tensor the caller would index: indexing costs
@@ -238,10 +219,8 @@ class _AudioFeatureFunction(torch.autograd.Function):
         dev = x.device
         g = torch.stack([gi.float().reshape(()) for gi in grad_each]).contiguous()
         gx = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_afloss_backward(_cabi.ptr(x), _cabi.ptr(y), bs, n, w, _cabi.ptr(tables), _cabi.ptr(fb), _cabi.ptr(g),
-                                               _cabi.ptr(gx), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev)),
-                       "mst_afloss_backward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_backward(x, y, bs, n, w, tables, fb, g, gx, ws, nbytes, st)
         return gx.view(shape), None, None, None
 
 

@@ -16,7 +16,6 @@ AdvancedMixConsole with every other stage switched off.
 """
 from __future__ import annotations
 
-import ctypes
 from collections.abc import Mapping
 
 import torch
@@ -159,7 +158,7 @@ class _ConsoleFunction(torch.autograd.Function):
             desc = _desc.make_desc(console.param_ranges, console.sample_rate, bs, n_tracks, n, row_stride, word,
                                    identity_ranges=denormalized, fx_ir_samples=console.fx_ir_samples,
                                    fx_bandpass_taps=console.fx_bandpass_taps)
-            nbytes = lib.mst_console_workspace_bytes(ctypes.byref(desc))
+            nbytes = lib.mst_console_workspace_bytes(desc)
             if nbytes == 0:
                 raise RuntimeError("mst_console_workspace_bytes rejected the configuration")
             if len(console._desc_cache) > 64:
@@ -178,29 +177,16 @@ class _ConsoleFunction(torch.autograd.Function):
         mixed = torch.empty(bs, 2, n_tracks, n, dtype=torch.float32, device=dev) if want_mixed else None
         status = console._status_word(dev)
         mirror = console._status_mirror(dev) if console.validate == "sync" and not torch.cuda.is_current_stream_capturing() else None
-        with torch.cuda.device(dev):
+        head = (desc, rows, tp, fp, mp, fx, mix, mixed, status, ws, nbytes)  # what the three forms of the forward share; fx None = NULL
+        with _hip.launch_on(dev) as st:
             if mirror is not None:
                 # validate="sync": the range check's verdict is copied to pinned host memory right behind the launch that forms it, the
                 # rest of the forward is enqueued behind that copy, and the host waits for the COPY - not for the mix
-                rc = lib.mst_console_forward_mirrored(
-                    ctypes.byref(desc), _cabi.ptr(rows), _cabi.ptr(tp), _cabi.ptr(fp), _cabi.ptr(mp),
-                    ctypes.byref(fx) if fx is not None else None, _cabi.ptr(mix),
-                    _cabi.ptr(mixed), _cabi.ptr(status), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev),
-                    ctypes.c_void_p(mirror[0].data_ptr()), ctypes.c_void_p(mirror[1].cuda_event),
-                )
-            elif split:
-                rc = lib.mst_console_forward_overlapped(
-                    ctypes.byref(desc), _cabi.ptr(rows), _cabi.ptr(tp), _cabi.ptr(fp), _cabi.ptr(mp), None, _cabi.ptr(mix),
-                    _cabi.ptr(mixed), _cabi.ptr(status), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev),
-                    ctypes.byref(_overlap_handles(dev)),
-                )
+                lib.mst_console_forward_mirrored(*head, st, mirror[0], mirror[1].cuda_event)
+            elif split:  # only ever without the fx bus
+                lib.mst_console_forward_overlapped(*head, st, _overlap_handles(dev))
             else:
-                rc = lib.mst_console_forward(
-                    ctypes.byref(desc), _cabi.ptr(rows), _cabi.ptr(tp), _cabi.ptr(fp), _cabi.ptr(mp),
-                    ctypes.byref(fx) if fx is not None else None, _cabi.ptr(mix),
-                    _cabi.ptr(mixed), _cabi.ptr(status), _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev),
-                )
-        _hip.check(rc, "mst_console_forward")
+                lib.mst_console_forward(*head, st)
         console._note_status(status, mirror)
         ctx.prep_event = None
         if need_grad and console.overlap_backward_prepare and not torch.cuda.is_current_stream_capturing():
@@ -208,9 +194,8 @@ class _ConsoleFunction(torch.autograd.Function):
             # now, where they run beside whatever the caller puts between the two calls (the loss), instead of on the critical path.
             cur, aux = torch.cuda.current_stream(dev), _aux_stream(dev)
             aux.wait_stream(cur)
-            with torch.cuda.device(dev):
-                rc = lib.mst_console_backward_prepare(ctypes.byref(desc), _cabi.ptr(ws), nbytes, ctypes.c_void_p(aux.cuda_stream))
-            _hip.check(rc, "mst_console_backward_prepare")
+            with torch.cuda.device(dev):  # on the side stream, not on the caller's
+                lib.mst_console_backward_prepare(desc, ws, nbytes, aux.cuda_stream)
             ctx.prep_event = aux.record_event()
             ws.record_stream(aux)
         if need_grad:
@@ -250,21 +235,12 @@ class _ConsoleFunction(torch.autograd.Function):
             prepared.flags |= _cabi.BWD_PREPARED
             desc = prepared
         # fx bus off: the fx parameters never reach the mix - their gradient is None, as in the reference (no zero fill)
-        with torch.cuda.device(dev):
-            if ctx.split:
-                rc = lib.mst_console_backward_overlapped(
-                    ctypes.byref(desc), _cabi.ptr(rows), _cabi.ptr(tp), _cabi.ptr(fp), _cabi.ptr(mp), None, _cabi.ptr(grad_mix),
-                    _cabi.ptr(grad_mixed), _cabi.ptr(g_tp), None, _cabi.ptr(g_mp), _cabi.ptr(g_tracks), _cabi.ptr(ctx.status), _cabi.ptr(ws),
-                    ctx.nbytes, _hip.current_stream_ptr(dev), ctypes.byref(_overlap_handles(dev)),
-                )
+        head = (desc, rows, tp, fp, mp, fx, grad_mix, grad_mixed, g_tp, g_fx, g_mp, g_tracks, ctx.status, ws, ctx.nbytes)
+        with _hip.launch_on(dev) as st:
+            if ctx.split:  # only ever without the fx bus: fx and g_fx are None
+                lib.mst_console_backward_overlapped(*head, st, _overlap_handles(dev))
             else:
-                rc = lib.mst_console_backward(
-                    ctypes.byref(desc), _cabi.ptr(rows), _cabi.ptr(tp), _cabi.ptr(fp), _cabi.ptr(mp),
-                    ctypes.byref(fx) if fx is not None else None, _cabi.ptr(grad_mix), _cabi.ptr(grad_mixed), _cabi.ptr(g_tp),
-                    _cabi.ptr(g_fx) if ctx.fx_on else None, _cabi.ptr(g_mp), _cabi.ptr(g_tracks), _cabi.ptr(ctx.status), _cabi.ptr(ws),
-                    ctx.nbytes, _hip.current_stream_ptr(dev),
-                )
-        _hip.check(rc, "mst_console_backward")
+                lib.mst_console_backward(*head, st)
         # no readback here: a backward whose in-launch exchange gave up has raised the (sticky) status word - the next forward's check
         # (validate="sync") or check_parameters() raises; a host sync inside every backward would stall the autograd thread
         return g_tracks, g_tp, g_fx, g_mp, None, None, None, None, None
@@ -377,7 +353,8 @@ class AdvancedMixConsole(torch.nn.Module):
         self.fx_ir_samples, self.fx_bandpass_taps = 65536, 1023
         self.fx_noise = None
         self.supports_fx_bus = True
-        self._fx_cache = {}
+        self._fx_cache = {}    # engine tables per (device, taps, sample rate)
+        self._fx_filters = {}  # the octave-band filterbank beside them, same key
         self._status = {}
         self._mirror = {}
         self._affine_cache = {}
@@ -386,7 +363,7 @@ class AdvancedMixConsole(torch.nn.Module):
 
     # per-device / per-signature caches (status words, pinned mirrors with their events, descriptors, constant tables) are not module
     # state: copy.deepcopy / pickling of a console that has already run gets fresh, empty ones (a torch.cuda.Event does not pickle)
-    _CACHES = ("_fx_cache", "_status", "_mirror", "_affine_cache", "_desc_cache")
+    _CACHES = ("_fx_cache", "_fx_filters", "_status", "_mirror", "_affine_cache", "_desc_cache")
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -447,13 +424,10 @@ class AdvancedMixConsole(torch.nn.Module):
 
         lib = _hip.lib()
         key = (str(device), self.fx_bandpass_taps, float(self.sample_rate))
-        if key not in self._fx_cache:
-            filters = octave_band_filterbank(self.fx_bandpass_taps, self.sample_rate).contiguous().to(device)
-            tables = torch.empty(lib.mst_console_fx_tables_bytes() // 4, dtype=torch.float32, device=device)
-            with torch.cuda.device(device):
-                _hip.check(lib.mst_console_fx_init_tables(_cabi.ptr(tables), _hip.current_stream_ptr(device)), "mst_console_fx_init_tables")
-            self._fx_cache[key] = (filters, tables)
-        filters, tables = self._fx_cache[key]
+        tables = _hip.device_tables(self._fx_cache, key, device, lib.mst_console_fx_tables_bytes, lib.mst_console_fx_init_tables)
+        filters = self._fx_filters.get(key)
+        if filters is None:
+            filters = self._fx_filters[key] = octave_band_filterbank(self.fx_bandpass_taps, self.sample_rate).contiguous().to(device)
         shape = (bs * 2, 12, self.fx_ir_samples + self.fx_bandpass_taps - 1)
         if self.fx_noise is not None:
             noise = self.fx_noise.to(device=device, dtype=torch.float32).contiguous()
@@ -660,22 +634,15 @@ class SpectrogramEncoder(torch.nn.Module):
         _hip.require_cuda(x)
         lib = _hip.lib()
         dev = x.device
-        key = str(dev)
-        tables = self._TABLES.get(key)
-        if tables is None:
-            tables = torch.empty(lib.mst_spectrogram_tables_bytes() // 4, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _hip.check(lib.mst_spectrogram_init_tables(_cabi.ptr(tables), _hip.current_stream_ptr(dev)), "mst_spectrogram_init_tables")
-            self._TABLES[key] = tables
+        tables = _hip.device_tables(self._TABLES, str(dev), dev, lib.mst_spectrogram_tables_bytes, lib.mst_spectrogram_init_tables)
         if x.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("SpectrogramEncoder (MI355X build): the STFT front end has no adjoint - the waveform gets no gradient "
                                       "(the reference never asks for one); detach() the input or run under torch.no_grad()")
         x = x.detach().float().contiguous()
         rows, n = x.shape
         spec = torch.empty(rows, 1 + n // self.hop_length, self.n_fft // 2 + 1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_spectrogram_forward(_cabi.ptr(x), rows, n, self.n_fft, self.hop_length, _cabi.ptr(tables), _cabi.ptr(spec),
-                                                   _hip.current_stream_ptr(dev)), "mst_spectrogram_forward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_spectrogram_forward(x, rows, n, self.n_fft, self.hop_length, tables, spec, st)
         return spec
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -16,8 +16,6 @@ the fp32 path's parity bounds at 0.84x its time; bf16x3 (~2^-17 per product) run
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
@@ -144,6 +142,37 @@ class _StatSync:
             raise self.error
 
 
+def _params_struct(keep, rmean, rvar):
+    """``mst_cnn14_params`` of the 38 parameters in ABI order (12 conv weights, 12 BN weights, 12 BN biases, fc weight, fc bias) and
+    the running statistics of the twelve BatchNorms."""
+    prm = _cabi.Cnn14Params()
+    for i in range(12):
+        prm.conv_w[i], prm.bn_gamma[i], prm.bn_beta[i] = keep[i].data_ptr(), keep[12 + i].data_ptr(), keep[24 + i].data_ptr()
+        prm.bn_mean[i], prm.bn_var[i] = rmean[i].data_ptr(), rvar[i].data_ptr()
+    prm.fc_w, prm.fc_b = keep[36].data_ptr(), keep[37].data_ptr()
+    return prm
+
+
+def _grads_struct(grads):
+    """``mst_cnn14_grads`` of 38 gradient buffers in the same order."""
+    gr = _cabi.Cnn14Grads()
+    for i in range(12):
+        gr.conv_w[i], gr.bn_gamma[i], gr.bn_beta[i] = grads[i].data_ptr(), grads[12 + i].data_ptr(), grads[24 + i].data_ptr()
+    gr.fc_w, gr.fc_b = grads[36].data_ptr(), grads[37].data_ptr()
+    return gr
+
+
+def _launch_synced(fn, dev, sync, *args):
+    """``fn(*args, stream, sync hook, NULL)`` of a ``mst_cnn14_*_sync`` entry; ``sync`` is the call's ``_StatSync`` or None (one rank).
+    An exception the hook caught takes precedence over the status the call then returns."""
+    try:
+        with _hip.launch_on(dev) as st:
+            fn(*args, st, sync.fn if sync else _cabi.SYNC_FN(), None)
+    finally:
+        if sync:
+            sync.check()
+
+
 class _Cnn14Function(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, module, training, *params):
@@ -161,7 +190,7 @@ class _Cnn14Function(torch.autograd.Function):
             _sync_count_check(group, n, dev)
         desc = _cabi.Cnn14Desc(n, frames, bins, module.fc.out_features, PRECISIONS[module.precision], int(training),
                                float(module.conv_block1.bn1.eps), world)
-        nbytes = lib.mst_cnn14_workspace_bytes(ctypes.byref(desc))
+        nbytes = lib.mst_cnn14_workspace_bytes(desc)
         if nbytes == 0:
             raise ValueError(f"Cnn14: unsupported spectrogram size {(frames, bins)} (six pooling stages need >= 128 frames x 1024 bins)")
         convs, gammas, betas = params[0:12], params[12:24], params[24:36]
@@ -169,25 +198,12 @@ class _Cnn14Function(torch.autograd.Function):
         keep = [t.detach().float().contiguous() for t in (*convs, *gammas, *betas, fc_w, fc_b)]
         rmean = [bn.running_mean.detach().float().contiguous() for bn in bns]
         rvar = [bn.running_var.detach().float().contiguous() for bn in bns]
-        prm = _cabi.Cnn14Params()
-        for i in range(12):
-            prm.conv_w[i] = keep[i].data_ptr()
-            prm.bn_gamma[i] = keep[12 + i].data_ptr()
-            prm.bn_beta[i] = keep[24 + i].data_ptr()
-            prm.bn_mean[i] = rmean[i].data_ptr()
-            prm.bn_var[i] = rvar[i].data_ptr()
-        prm.fc_w, prm.fc_b = keep[36].data_ptr(), keep[37].data_ptr()
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         embed = torch.empty(n, module.fc.out_features, dtype=torch.float32, device=dev)
         stats = torch.empty(12, 2, 2048, dtype=torch.float32, device=dev) if training else None
         spec = spec.float().contiguous()
-        sync = _StatSync(ws, group) if world > 1 else None
-        with torch.cuda.device(dev):
-            rc = lib.mst_cnn14_forward_sync(ctypes.byref(desc), _cabi.ptr(spec), ctypes.byref(prm), _cabi.ptr(embed), _cabi.ptr(stats),
-                                            _cabi.ptr(ws), nbytes, _hip.current_stream_ptr(dev), sync.fn if sync else _cabi.SYNC_FN(), None)
-        if sync:
-            sync.check()
-        _hip.check(rc, "mst_cnn14_forward")
+        _launch_synced(lib.mst_cnn14_forward_sync, dev, _StatSync(ws, group) if world > 1 else None, desc, spec,
+                       _params_struct(keep, rmean, rvar), embed, stats, ws, nbytes)
         ctx.desc, ctx.nbytes, ctx.dev, ctx.group = desc, nbytes, dev, group
         # the backward reads mean / invstd from the workspace; the running statistics (updated in place by the module right
         # after a training-mode call) are only handed over again, never read in training mode
@@ -204,22 +220,10 @@ class _Cnn14Function(torch.autograd.Function):
         rmean, rvar = ctx.running
         lib = _hip.lib()
         dev = ctx.dev
-        prm, gr = _cabi.Cnn14Params(), _cabi.Cnn14Grads()
         grads = [torch.empty_like(t) for t in keep]
-        for i in range(12):
-            prm.conv_w[i], prm.bn_gamma[i], prm.bn_beta[i] = keep[i].data_ptr(), keep[12 + i].data_ptr(), keep[24 + i].data_ptr()
-            prm.bn_mean[i], prm.bn_var[i] = rmean[i].data_ptr(), rvar[i].data_ptr()
-            gr.conv_w[i], gr.bn_gamma[i], gr.bn_beta[i] = grads[i].data_ptr(), grads[12 + i].data_ptr(), grads[24 + i].data_ptr()
-        prm.fc_w, prm.fc_b = keep[36].data_ptr(), keep[37].data_ptr()
-        gr.fc_w, gr.fc_b = grads[36].data_ptr(), grads[37].data_ptr()
         g = g_embed.float().contiguous()
-        sync = _StatSync(ws, ctx.group) if ctx.desc.world > 1 else None
-        with torch.cuda.device(dev):
-            rc = lib.mst_cnn14_backward_sync(ctypes.byref(ctx.desc), _cabi.ptr(spec), ctypes.byref(prm), _cabi.ptr(g), ctypes.byref(gr),
-                                             _cabi.ptr(ws), ctx.nbytes, _hip.current_stream_ptr(dev), sync.fn if sync else _cabi.SYNC_FN(), None)
-        if sync:
-            sync.check()
-        _hip.check(rc, "mst_cnn14_backward")
+        _launch_synced(lib.mst_cnn14_backward_sync, dev, _StatSync(ws, ctx.group) if ctx.desc.world > 1 else None, ctx.desc, spec,
+                       _params_struct(keep, rmean, rvar), g, _grads_struct(grads), ws, ctx.nbytes)
         return (None, None, None, *grads)
 
 

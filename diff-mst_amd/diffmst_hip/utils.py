@@ -4,7 +4,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _cabi, _hip
+from . import _hip
 
 
 class _PeakNormalize(torch.autograd.Function):
@@ -28,9 +28,8 @@ class _PeakNormalize(torch.autograd.Function):
         nbytes = lib.mst_peak_normalize_workspace_bytes(bs, n)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         y = torch.empty_like(xc)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_peak_normalize_forward(_cabi.ptr(xc), _cabi.ptr(y), bs, n, _cabi.ptr(ws), nbytes,
-                                                      _hip.current_stream_ptr(dev)), "mst_peak_normalize_forward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_peak_normalize_forward(xc, y, bs, n, ws, nbytes, st)
         ctx.save_for_backward(xc, ws)
         ctx.nbytes = nbytes
         ctx.shape = shape
@@ -48,9 +47,8 @@ class _PeakNormalize(torch.autograd.Function):
             g = torch.nn.functional.pad(g, (0, 2 * n - g.size(1)))
         g = g.contiguous().view(xc.shape)
         dx = torch.empty_like(xc)
-        with torch.cuda.device(dev):
-            _hip.check(lib.mst_peak_normalize_backward(_cabi.ptr(xc), _cabi.ptr(g), _cabi.ptr(dx), bs, n, _cabi.ptr(ws),
-                                                       ctx.nbytes, _hip.current_stream_ptr(dev)), "mst_peak_normalize_backward")
+        with _hip.launch_on(dev) as st:
+            lib.mst_peak_normalize_backward(xc, g, dx, bs, n, ws, ctx.nbytes, st)
         shape = ctx.shape
         return dx.view(shape[0], -1)[:, : shape[1] * shape[2]].reshape(shape)
 
@@ -69,19 +67,10 @@ _LOUDNESS_TABLES = {}
 
 def _loudness_tables(device, sample_rate):
     """Block boundaries, K-weighting coefficients and transition-matrix powers: built once per (device, rate)."""
-    key = (str(device), int(sample_rate))
-    t = _LOUDNESS_TABLES.get(key)
-    if t is None:
-        lib = _hip.lib()
-        nbytes = lib.mst_loudness_tables_bytes(int(sample_rate))
-        if nbytes == 0:
-            raise ValueError(f"unsupported sample rate {sample_rate} (the device meter needs at least 20500 Hz)")
-        t = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _hip.check(lib.mst_loudness_init_tables(int(sample_rate), _cabi.ptr(t), _hip.current_stream_ptr(device)),
-                       "mst_loudness_init_tables")
-        _LOUDNESS_TABLES[key] = t
-    return t
+    lib = _hip.lib()
+    return _hip.device_tables(_LOUDNESS_TABLES, (str(device), int(sample_rate)), device, lib.mst_loudness_tables_bytes,
+                              lib.mst_loudness_init_tables, int(sample_rate), dtype=torch.uint8,
+                              unsupported=f"unsupported sample rate {sample_rate} (the device meter needs at least 20500 Hz)")
 
 
 def _forward_only(x, what):
@@ -123,10 +112,8 @@ def _meter(x3, sample_rate, return_blocks):
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     lufs = torch.empty(rows, dtype=torch.float32, device=dev)
     blocks = torch.empty(rows, nblocks, dtype=torch.float32, device=dev) if return_blocks else None
-    with torch.cuda.device(dev):
-        _hip.check(lib.mst_loudness_integrated(_cabi.ptr(x3), rows, chs, n, x3.stride(0), x3.stride(1), int(sample_rate),
-                                               _cabi.ptr(tables), _cabi.ptr(lufs), _cabi.ptr(blocks), _cabi.ptr(ws), nbytes,
-                                               _hip.current_stream_ptr(dev)), "mst_loudness_integrated")
+    with _hip.launch_on(dev) as st:
+        lib.mst_loudness_integrated(x3, rows, chs, n, x3.stride(0), x3.stride(1), int(sample_rate), tables, lufs, blocks, ws, nbytes, st)
     return lufs, blocks
 
 
@@ -166,10 +153,8 @@ def _apply_loudness_gain(x3, lufs, target_lufs, floor_lufs):
     y = torch.empty(rows, chs, n, dtype=torch.float32, device=dev)
     keep = torch.empty(rows, dtype=torch.uint8, device=dev)
     floor = float("-inf") if floor_lufs is None else float(floor_lufs)
-    with torch.cuda.device(dev):
-        _hip.check(lib.mst_loudness_normalize(_cabi.ptr(x3), _cabi.ptr(y), _cabi.ptr(lufs), rows, chs, n, x3.stride(0), x3.stride(1),
-                                              float(target_lufs), floor, _cabi.ptr(keep), _hip.current_stream_ptr(dev)),
-                   "mst_loudness_normalize")
+    with _hip.launch_on(dev) as st:
+        lib.mst_loudness_normalize(x3, y, lufs, rows, chs, n, x3.stride(0), x3.stride(1), float(target_lufs), floor, keep, st)
     return y, keep.bool()
 
 
@@ -221,19 +206,11 @@ def _resample_tables(device, orig_freq, new_freq):
 
     g = math.gcd(orig_freq, new_freq)
     key = (str(device), orig_freq // g, new_freq // g)
-    t = _RESAMPLE_TABLES.get(key)
-    if t is None:
-        lib = _hip.lib()
-        nbytes = lib.mst_resample_tables_bytes(orig_freq, new_freq)
-        if nbytes == 0:
-            raise ValueError(f"unsupported resampling ratio {orig_freq} -> {new_freq}: reduced to {key[1]}:{key[2]}, the device "
-                             "resampler takes reduced rates up to 1024 and at most 132 taps per output sample")
-        t = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _hip.check(lib.mst_resample_init_tables(orig_freq, new_freq, _cabi.ptr(t), _hip.current_stream_ptr(device)),
-                       "mst_resample_init_tables")
-        _RESAMPLE_TABLES[key] = t
-    return t
+    lib = _hip.lib()
+    return _hip.device_tables(_RESAMPLE_TABLES, key, device, lib.mst_resample_tables_bytes, lib.mst_resample_init_tables, orig_freq, new_freq,
+                              dtype=torch.uint8,
+                              unsupported=f"unsupported resampling ratio {orig_freq} -> {new_freq}: reduced to {key[1]}:{key[2]}, the device "
+                                          "resampler takes reduced rates up to 1024 and at most 132 taps per output sample")
 
 
 def _time_rows(x):
@@ -258,9 +235,8 @@ class _Resample(torch.autograd.Function):
             raise ValueError(f"unsupported resample call: {n} samples, {orig_freq} -> {new_freq}")
         y = torch.empty(n_rows, n_out, dtype=torch.float32, device=dev)
         if n_rows:
-            with torch.cuda.device(dev):
-                _hip.check(lib.mst_resample_forward(_cabi.ptr(rows), n_rows, n, rows.stride(0), orig_freq, new_freq, _cabi.ptr(tables),
-                                                    _cabi.ptr(y), _hip.current_stream_ptr(dev)), "mst_resample_forward")
+            with _hip.launch_on(dev) as st:
+                lib.mst_resample_forward(rows, n_rows, n, rows.stride(0), orig_freq, new_freq, tables, y, st)
         ctx.rates = (orig_freq, new_freq)
         ctx.in_shape, ctx.in_dtype = x.shape, x.dtype
         return y.view(*x.shape[:-1], n_out).to(x.dtype)
@@ -275,10 +251,9 @@ class _Resample(torch.autograd.Function):
         g2 = g.float().contiguous().view(-1, g.shape[-1])
         gx = torch.empty(g2.shape[0], n, dtype=torch.float32, device=dev)
         if g2.shape[0]:
-            with torch.cuda.device(dev):
-                _hip.check(lib.mst_resample_backward(_cabi.ptr(g2), g2.shape[0], n, orig_freq, new_freq,
-                                                     _cabi.ptr(_resample_tables(dev, orig_freq, new_freq)), _cabi.ptr(gx),
-                                                     _hip.current_stream_ptr(dev)), "mst_resample_backward")
+            tables = _resample_tables(dev, orig_freq, new_freq)
+            with _hip.launch_on(dev) as st:
+                lib.mst_resample_backward(g2, g2.shape[0], n, orig_freq, new_freq, tables, gx, st)
         return gx.view(ctx.in_shape).to(ctx.in_dtype), None, None
 
 

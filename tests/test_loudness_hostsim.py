@@ -32,21 +32,17 @@ _TABLES = {}
 
 
 def tables(L, rate):
-    from mst import _cabi
-
     if rate not in _TABLES:
         nbytes = L.mst_loudness_tables_bytes(rate)
         assert nbytes > 0
         t = torch.zeros(nbytes // 4, dtype=torch.int32)
-        assert L.mst_loudness_init_tables(rate, _cabi.ptr(t), None) == 0
+        L.mst_loudness_init_tables(rate, t, None)
         _TABLES[rate] = t
     return _TABLES[rate]
 
 
 def meter(L, x, rate):
     """x: float32 tensor (rows, channels, n), any row / channel stride -> (lufs (rows,), block loudness (rows, nb)) float64 numpy."""
-    from mst import _cabi
-
     rows, chs, n = x.shape
     assert x.stride(2) == 1
     nbytes = L.mst_loudness_workspace_bytes(rows, chs, n, rate)
@@ -55,9 +51,7 @@ def meter(L, x, rate):
     ws = torch.full((nbytes // 8 + 1,), float("nan"), dtype=torch.float64)  # the kernels must not rely on a cleared workspace
     lufs = torch.full((rows,), float("nan"))
     blocks = torch.full((rows, nb), float("nan"))
-    rc = L.mst_loudness_integrated(_cabi.ptr(x), rows, chs, n, x.stride(0), x.stride(1), rate, _cabi.ptr(tables(L, rate)),
-                                   _cabi.ptr(lufs), _cabi.ptr(blocks), _cabi.ptr(ws), nbytes, None)
-    assert rc == 0
+    L.mst_loudness_integrated(x, rows, chs, n, x.stride(0), x.stride(1), rate, tables(L, rate), lufs, blocks, ws, nbytes, None)
     return lufs.double().numpy(), blocks.double().numpy()
 
 
@@ -126,8 +120,6 @@ def test_meter_matches_the_float64_restatement(lib, rate, rows, chs, n, pad, see
 
 # ---- 3. edge cases ------------------------------------------------------------------------------------------------------------
 def test_silent_and_sub_gate_rows(lib):
-    from mst import _cabi
-
     n, rate = 30000, 44100
     x = torch.from_numpy(R.level_step_noise(4, 1, n, 21))
     x[1] = 0.0            # silence
@@ -142,21 +134,25 @@ def test_silent_and_sub_gate_rows(lib):
     y = torch.full((4, 1, n), float("nan"))
     keep = torch.full((4,), 7, dtype=torch.uint8)
     lt = torch.from_numpy(lufs).float()
-    assert lib.mst_loudness_normalize(_cabi.ptr(x), _cabi.ptr(y), _cabi.ptr(lt), 4, 1, n, x.stride(0), x.stride(1), -48.0, -80.0,
-                                      _cabi.ptr(keep), None) == 0
+    lib.mst_loudness_normalize(x, y, lt, 4, 1, n, x.stride(0), x.stride(1), -48.0, -80.0, keep, None)
     assert keep.tolist() == [1, 0, 0, 1]
     assert torch.isfinite(y).all() and not y[1].any() and not y[2].any() and y[0].any() and y[3].any()
 
 
 def test_short_signals_are_refused(lib):
     import mst.utils as U
+    from mst import _cabi
 
     assert lib.mst_loudness_workspace_bytes(1, 1, 17639, 44100) == 0 and lib.mst_loudness_num_blocks(17639, 44100) == 0
     assert lib.mst_loudness_workspace_bytes(1, 1, 17640, 44100) > 0 and lib.mst_loudness_num_blocks(17640, 44100) == 1
     assert lib.mst_loudness_workspace_bytes(1, 6, 70000, 44100) == 0      # five channels at most
     assert lib.mst_loudness_workspace_bytes(1, 1, 70000, 8000) == 0       # unsupported rate
-    assert lib.mst_loudness_integrated(None, 1, 1, 70000, 70000, 70000, 44100, None, None, None, None, 0, None) != 0
-    assert lib.mst_loudness_normalize(None, None, None, 1, 1, 70000, 70000, 70000, -48.0, -80.0, None, None) != 0
+    with pytest.raises(_cabi.AbiError) as e:
+        lib.mst_loudness_integrated(None, 1, 1, 70000, 70000, 70000, 44100, None, None, None, None, 0, None)
+    assert e.value.code != 0
+    with pytest.raises(_cabi.AbiError) as e:
+        lib.mst_loudness_normalize(None, None, None, 1, 1, 70000, 70000, 70000, -48.0, -80.0, None, None)
+    assert e.value.code != 0
     with pytest.raises(ValueError, match="Audio must have length greater than the block size."):
         U.integrated_loudness(torch.zeros(1, 17639))
     with pytest.raises(ValueError, match="Audio must have length greater than the block size."):
@@ -177,8 +173,6 @@ def test_two_calls_are_bit_identical(lib, rows):
 
 # ---- 4. normalisation ---------------------------------------------------------------------------------------------------------
 def test_normalize_gains(lib):
-    from mst import _cabi
-
     n, rate, target = 20001, 44100, -23.0
     full = torch.zeros(3, 2, n + 5)
     full[..., 1:n + 1] = torch.from_numpy(R.level_step_noise(3, 2, n, 41))
@@ -187,8 +181,7 @@ def test_normalize_gains(lib):
     lt = torch.from_numpy(lufs).float()
     y = torch.full((3, 2, n), float("nan"))
     keep = torch.zeros(3, dtype=torch.uint8)
-    assert lib.mst_loudness_normalize(_cabi.ptr(x), _cabi.ptr(y), _cabi.ptr(lt), 3, 2, n, x.stride(0), x.stride(1), target,
-                                      float("-inf"), _cabi.ptr(keep), None) == 0
+    lib.mst_loudness_normalize(x, y, lt, 3, 2, n, x.stride(0), x.stride(1), target, float("-inf"), keep, None)
     assert keep.tolist() == [1, 1, 1]
     gain = 10.0 ** ((target - lt.double().numpy()) / 20.0)  # float64, from the kernel's own L
     want = x.double().numpy() * gain.astype(np.float32).astype(np.float64)[:, None, None]

@@ -60,7 +60,7 @@ def test_forward_matches_the_float64_restatement(orig, new, record):
 
 def test_one_song_section():
     """8 x 524288 at 48000 -> 44100: against the float64 restatement, and the guard region behind a caller-owned output."""
-    from mst import _cabi, _hip
+    from mst import _hip
     from mst.utils import _resample_tables, resample
 
     orig, new, rows, n = 48000, 44100, 8, 524288
@@ -72,9 +72,8 @@ def test_one_song_section():
     n_out = lib.mst_resample_out_samples(n, orig, new)
     assert n_out == R.out_samples(n, orig, new)
     buf = torch.full((rows * n_out + 4096,), float("nan"), device=dev)
-    with torch.cuda.device(dev):
-        assert lib.mst_resample_forward(_cabi.ptr(xd), rows, n, n, orig, new, _cabi.ptr(_resample_tables(dev, orig, new)), _cabi.ptr(buf),
-                                        _hip.current_stream_ptr(dev)) == 0
+    with _hip.launch_on(dev) as st:
+        lib.mst_resample_forward(xd, rows, n, n, orig, new, _resample_tables(dev, orig, new), buf, st)
     assert torch.isnan(buf[rows * n_out:]).all()
     assert torch.equal(buf[: rows * n_out].view(rows, n_out), resample(xd, orig, new))
 

@@ -19,13 +19,11 @@ _TABLES = {}
 
 
 def tables(L, orig, new):
-    from mst import _cabi
-
     if (orig, new) not in _TABLES:
         nbytes = L.mst_resample_tables_bytes(orig, new)
         assert nbytes > 0
         t = torch.zeros(nbytes // 4, dtype=torch.int32)
-        assert L.mst_resample_init_tables(orig, new, _cabi.ptr(t), None) == 0
+        L.mst_resample_init_tables(orig, new, t, None)
         _TABLES[(orig, new)] = t
     return _TABLES[(orig, new)]
 
@@ -36,15 +34,12 @@ GUARD = 64
 def forward(L, x, orig, new):
     """x: float32 tensor (rows, n), unit sample stride, any row stride -> y (rows, n_out); the output buffer is pre-filled with
     NaN, must be overwritten completely and nothing may be written behind it."""
-    from mst import _cabi
-
     rows, n = x.shape
     assert x.stride(1) == 1 or n == 1
     n_out = L.mst_resample_out_samples(n, orig, new)
     assert n_out == R.out_samples(n, orig, new)
     buf = torch.full((rows * n_out + GUARD,), float("nan"))
-    rc = L.mst_resample_forward(_cabi.ptr(x), rows, n, x.stride(0), orig, new, _cabi.ptr(tables(L, orig, new)), _cabi.ptr(buf), None)
-    assert rc == 0
+    L.mst_resample_forward(x, rows, n, x.stride(0), orig, new, tables(L, orig, new), buf, None)
     assert torch.isnan(buf[rows * n_out:]).all(), "written past the output"
     y = buf[: rows * n_out].view(rows, n_out)
     assert torch.isfinite(y).all(), "output not fully written"
@@ -52,13 +47,10 @@ def forward(L, x, orig, new):
 
 
 def backward(L, g, n, orig, new):
-    from mst import _cabi
-
     rows, n_out = g.shape
     assert g.is_contiguous() and n_out == R.out_samples(n, orig, new)
     buf = torch.full((rows * n + GUARD,), float("nan"))
-    rc = L.mst_resample_backward(_cabi.ptr(g), rows, n, orig, new, _cabi.ptr(tables(L, orig, new)), _cabi.ptr(buf), None)
-    assert rc == 0
+    L.mst_resample_backward(g, rows, n, orig, new, tables(L, orig, new), buf, None)
     assert torch.isnan(buf[rows * n:]).all(), "written past grad_x"
     gx = buf[: rows * n].view(rows, n)
     assert torch.isfinite(gx).all(), "grad_x not fully written"
@@ -173,11 +165,20 @@ def test_unsupported_ratio_launches_nothing(lib):
     assert lib.mst_resample_tables_bytes(1024, 1) == 0       # 12413 taps per output
     assert lib.mst_resample_tables_bytes(1024, 1023) > 0 and lib.mst_resample_tables_bytes(3, 1024) > 0  # the corners of the domain
     x, y, t = torch.ones(1, 1000), torch.full((1100,), float("nan")), torch.zeros(64, dtype=torch.int32)
-    assert lib.mst_resample_init_tables(44101, 44100, _cabi.ptr(t), None) != 0 and not t.any()
-    assert lib.mst_resample_forward(_cabi.ptr(x), 1, 1000, 1000, 44101, 44100, _cabi.ptr(t), _cabi.ptr(y), None) != 0
-    assert lib.mst_resample_backward(_cabi.ptr(x), 1, 1000, 44101, 44100, _cabi.ptr(t), _cabi.ptr(y), None) != 0
+    with pytest.raises(_cabi.AbiError) as e:
+        lib.mst_resample_init_tables(44101, 44100, t, None)
+    assert e.value.code != 0
+    assert not t.any()
+    with pytest.raises(_cabi.AbiError) as e:
+        lib.mst_resample_forward(x, 1, 1000, 1000, 44101, 44100, t, y, None)
+    assert e.value.code != 0
+    with pytest.raises(_cabi.AbiError) as e:
+        lib.mst_resample_backward(x, 1, 1000, 44101, 44100, t, y, None)
+    assert e.value.code != 0
     assert torch.isnan(y).all()
-    assert lib.mst_resample_forward(None, 1, 1000, 1000, 48000, 44100, None, None, None) != 0
+    with pytest.raises(_cabi.AbiError) as e:
+        lib.mst_resample_forward(None, 1, 1000, 1000, 48000, 44100, None, None, None)
+    assert e.value.code != 0
 
 
 @pytest.mark.parametrize("orig,new", [(1024, 1023), (3, 1024), (1000, 97)])
