@@ -1,0 +1,178 @@
+// mst_opt.hip - the bookkeeping of per-song mix optimisation (diffmst_hip/online.py; the loop of the reference's scripts/online.py:71-106)
+// as ONE launch per iteration: chain dL/dp through the sigmoid, apply Adam to the logits, emit the next iteration's (0,1) parameters,
+// append the loss terms to a device-side history and advance the step count - nothing of it passes through the host.
+// PARITY UNPINNED: the arithmetic restates torch.optim.Adam (single-tensor path, defaults: no weight decay, no amsgrad) behind
+// torch.sigmoid from torch's published source, operation by operation as the CPU kernels evaluate them:
+//     g  = (dp (1 - p)) p                                   sigmoid_backward, with the p the console consumed
+//     m  = m + w1 (g - m)              w1 = fp32(1 - b1)     exp_avg.lerp_(grad, 1 - beta1)  (the branch torch takes for w1 < 0.5)
+//     v  = v b2 + (w2 g) g             w2 = fp32(1 - b2)     exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+//     th = th + (s m) / (sqrt(v) / c2 + eps)                 s = fp32(-lr / (1 - b1^t)), c2 = fp32(sqrt(1 - b2^t)), both from float64
+//     p  = 1 / (1 + exp(-th))
+// Every rounding is written out: this unit is compiled with -ffp-contract=off (Makefile).
+// A song has 27 T + 51 parameters, so the whole step is one workgroup that loops.  Its first pass looks at every gradient element and
+// loss term; a workgroup-wide flag in LDS carries "something is not finite" to the second pass, which then leaves every coordinate
+// alone (torch would spread the NaN through all of them).  Every lane reads and writes only the coordinates i = tid + k 256 < count of
+// a segment; the history row is written by lane 0, 1 + n_terms floats.
+#include <math.h>
+
+#include "mst_common.h"
+
+namespace mst {
+
+constexpr int kOptWG = 256;
+constexpr int kOptHdr = 16;               // int32 words in front of the moments (include/diffmst_hip.h)
+constexpr int64_t kOptMaxParams = 1 << 20;
+
+struct OptArgs {
+    float* theta[MST_OPT_MAX_SEGMENTS];
+    float* p[MST_OPT_MAX_SEGMENTS];
+    const float* grad_p[MST_OPT_MAX_SEGMENTS];
+    int32_t count[MST_OPT_MAX_SEGMENTS];
+    int32_t n_segments;
+    const float* term[MST_OPT_MAX_TERMS];
+    int32_t n_terms;
+    int32_t n_params;
+};
+
+__device__ __forceinline__ bool opt_finite(float x) { return (__float_as_int(x) & 0x7f800000) != 0x7f800000; }
+__device__ __forceinline__ float opt_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// state words [0, 16 + 2 n) <- 0, p <- sigmoid(theta)
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_init(OptArgs a, int32_t* __restrict__ state) {
+    const int tid = threadIdx.x;
+    const int words = kOptHdr + 2 * a.n_params;
+    for (int w = tid; w < words; w += kOptWG) state[w] = 0;
+#pragma unroll
+    for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
+        if (s >= a.n_segments) break;
+        const float* __restrict__ th = a.theta[s];
+        float* __restrict__ p = a.p[s];
+        for (int i = tid; i < a.count[s]; i += kOptWG) p[i] = opt_sigmoid(th[i]);
+    }
+}
+
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __restrict__ row, double lr, double beta1, double beta2,
+                                                            float eps, int32_t* __restrict__ state) {
+    __shared__ int s_bad;
+    __shared__ float s_step, s_c2;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
+        if (s >= a.n_segments) break;
+        const float* __restrict__ dp = a.grad_p[s];
+        if (!dp) continue;
+        for (int i = tid; i < a.count[s]; i += kOptWG) bad |= !opt_finite(dp[i]);
+    }
+    if (tid < a.n_terms) bad |= !opt_finite(*a.term[tid]);
+    if (bad) atomicMax(&s_bad, 1);
+    if (tid == 0) {  // the two bias corrections of step t = state[0] + 1, in float64, rounded once
+        const double t = (double)(state[0] + 1);
+        s_step = (float)(-(lr / (1.0 - pow(beta1, t))));
+        s_c2 = (float)sqrt(1.0 - pow(beta2, t));
+    }
+    __syncthreads();
+    const bool stop = s_bad != 0;
+    if (tid == 0) {
+        float sum = 0.0f;  // the script's `loss = 0; loss += value`, left to right
+        for (int k = 0; k < a.n_terms; ++k) {
+            const float term = *a.term[k];
+            sum += term;
+            row[1 + k] = term;
+        }
+        row[0] = sum;
+        const int32_t iteration = state[3];
+        if (stop && !state[1]) {
+            state[1] = MST_OPT_STATUS_NONFINITE;
+            state[2] = iteration;
+        }
+        state[3] = iteration + 1;
+        if (!stop) state[0] += 1;
+    }
+    if (stop) return;
+    const float step = s_step, c2 = s_c2, b2 = (float)beta2, w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2);
+    float* __restrict__ m_all = reinterpret_cast<float*>(state + kOptHdr);
+    float* __restrict__ v_all = m_all + a.n_params;
+    int at = 0;
+#pragma unroll
+    for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
+        if (s >= a.n_segments) break;
+        const int n = a.count[s];
+        const float* __restrict__ dp = a.grad_p[s];
+        if (dp) {  // a NULL gradient is a parameter without .grad: torch skips it, its logits, moments and p keep their bits
+            float* __restrict__ th = a.theta[s];
+            float* __restrict__ p = a.p[s];
+            float* __restrict__ m = m_all + at;
+            float* __restrict__ v = v_all + at;
+            for (int i = tid; i < n; i += kOptWG) {
+                const float pi = p[i];
+                const float g = (dp[i] * (1.0f - pi)) * pi;
+                const float mi = m[i] + w1 * (g - m[i]);
+                const float vi = v[i] * b2 + (w2 * g) * g;
+                const float ti = th[i] + (step * mi) / (sqrtf(vi) / c2 + eps);
+                m[i] = mi;
+                v[i] = vi;
+                th[i] = ti;
+                p[i] = opt_sigmoid(ti);
+            }
+        }
+        at += n;
+    }
+}
+
+namespace {
+// the segment table as kernel arguments; false for what the kernels do not support
+bool opt_args(const mst_logit_adam_segment* segments, int32_t n_segments, OptArgs& a) {
+    if (!segments || n_segments < 1 || n_segments > MST_OPT_MAX_SEGMENTS) return false;
+    a = OptArgs{};
+    int64_t total = 0;
+    for (int s = 0; s < n_segments; ++s) {
+        const mst_logit_adam_segment& g = segments[s];
+        if (!g.theta || !g.p || g.count < 1 || g.count > kOptMaxParams || ((uintptr_t)g.theta & 3) || ((uintptr_t)g.p & 3) ||
+            ((uintptr_t)g.grad_p & 3))
+            return false;
+        a.theta[s] = g.theta;
+        a.p[s] = g.p;
+        a.grad_p[s] = g.grad_p;
+        a.count[s] = (int32_t)g.count;
+        total += g.count;
+    }
+    if (total > kOptMaxParams) return false;
+    a.n_segments = n_segments;
+    a.n_params = (int32_t)total;
+    return true;
+}
+}  // namespace
+}  // namespace mst
+
+using namespace mst;
+
+extern "C" size_t mst_logit_adam_state_bytes(int64_t n_params) {
+    if (n_params < 1 || n_params > kOptMaxParams) return 0;
+    return ((size_t)kOptHdr + 2 * (size_t)n_params) * 4;
+}
+extern "C" int mst_logit_adam_init(const mst_logit_adam_segment* segments, int32_t n_segments, void* state, void* stream) {
+    OptArgs a;
+    if (!opt_args(segments, n_segments, a) || !state || ((uintptr_t)state & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_logit_adam_init, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, (int32_t*)state);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_logit_adam_step(const mst_logit_adam_segment* segments, int32_t n_segments, const float* const* loss_terms,
+                                   int32_t n_terms, float* history_row, double lr, double beta1, double beta2, double eps, void* state,
+                                   void* stream) {
+    OptArgs a;
+    if (!opt_args(segments, n_segments, a) || !state || ((uintptr_t)state & 3) || !history_row || ((uintptr_t)history_row & 3) ||
+        !loss_terms || n_terms < 1 || n_terms > MST_OPT_MAX_TERMS)
+        return hipErrorInvalidValue;
+    if (!(lr > 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0)) return hipErrorInvalidValue;
+    for (int k = 0; k < n_terms; ++k) {
+        if (!loss_terms[k] || ((uintptr_t)loss_terms[k] & 3)) return hipErrorInvalidValue;
+        a.term[k] = loss_terms[k];
+    }
+    a.n_terms = n_terms;
+    hipLaunchKernelGGL(k_logit_adam_step, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, history_row, lr, beta1, beta2, (float)eps,
+                       (int32_t*)state);
+    return (int)hipGetLastError();
+}

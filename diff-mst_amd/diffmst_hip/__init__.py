@@ -8,6 +8,7 @@ The hot-path classes and functions of the reference, under their reference names
     diffmst_hip.loss.MultiResolutionSTFTLoss        <- auraloss.freq.MultiResolutionSTFTLoss (configs/models/naive.yaml:55)
     diffmst_hip.utils.batch_stereo_peak_normalize   <- reference mst/utils.py:14-29
     diffmst_hip.system.CommonStep                   <- call order of reference mst/system.py:102-407, without Lightning
+    diffmst_hip.online.optimize / render_blocks     <- reference scripts/online.py:15-123, :325-346
 
 All numerical work runs in hand-written HIP kernels for gfx950 behind the C ABI of
 ``include/diffmst_hip.h``; there is no CPU fallback.
@@ -25,7 +26,7 @@ import sys
 __version__ = "0.2.0"
 
 from . import _cabi, _desc, _hip, filter, loss, mixing, modules, panns, utils  # noqa: E402,F401
-from . import system  # noqa: E402,F401
+from . import online, system  # noqa: E402,F401
 
 # (module of the reference, attribute, replacement)
 _TARGETS = (

@@ -25,7 +25,7 @@ NO_RANGE_CHECK = 0x400
 BWD_PREPARED = 0x800
 SPLIT_BATCH = 0x1000
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class ConsoleDesc(C.Structure):
@@ -118,6 +118,13 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
     _fields_ = [(name, C.c_void_p) for name in CTRL_FIELDS]
 
 
+OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
+
+
+class LogitAdamSegment(C.Structure):  # mirrors mst_logit_adam_segment
+    _fields_ = [("theta", C.c_void_p), ("p", C.c_void_p), ("grad_p", C.c_void_p), ("count", C.c_int64)]
+
+
 def ptr(t):
     """Address of a tensor (device memory, or host memory in the simulator tests) as a ``c_void_p``; NULL for None."""
     return None if t is None else C.c_void_p(t.data_ptr())
@@ -194,6 +201,10 @@ SIGNATURES = {
     "mst_resample_out_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "mst_resample_forward": (STATUS, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _S]),
     "mst_resample_backward": (STATUS, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _S]),
+    "mst_logit_adam_state_bytes": (C.c_size_t, [C.c_int64]),
+    "mst_logit_adam_init": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, _P, _S]),
+    "mst_logit_adam_step": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _P, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, _P, _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

@@ -312,6 +312,49 @@ int mst_resample_backward(const float* grad_y, int32_t rows, int64_t n_samples, 
                           const void* tables, float* grad_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-song mix optimisation (ABI v12): the bookkeeping of one iteration of the loop in the reference's scripts/online.py:71-106 -
+ * console parameters p = sigmoid(theta), torch.optim.Adam on the logits theta - as ONE launch, so that a loop of console forward,
+ * loss, backward and this step never waits for the host.  PARITY UNPINNED: a restatement of torch.optim.Adam (single-tensor path at
+ * its defaults: no weight decay, no amsgrad, not maximising) and torch.sigmoid from torch's published source.
+ *   segments     host array of 1..MST_OPT_MAX_SEGMENTS parameter tensors (copied into the launch, need not outlive the call).  Per
+ *                segment, all device pointers, dense fp32, `count` elements, caller-owned:
+ *                  theta   the logits, updated in place
+ *                  p       sigmoid(theta): written by mst_logit_adam_init, read (as the value the forward consumed) and rewritten
+ *                          by mst_logit_adam_step
+ *                  grad_p  dL/dp, read-only, or NULL: a parameter without gradient, which keeps theta, its moments and p bit for
+ *                          bit (torch skips a parameter whose .grad is None)
+ *   state        mst_logit_adam_state_bytes(sum of the counts) bytes, caller-owned, opaque but for its first four int32 words:
+ *                  [0] t, the number of updates applied   [1] status, 0 or MST_OPT_STATUS_NONFINITE, sticky
+ *                  [2] the index of the iteration that set the status   [3] the number of mst_logit_adam_step calls so far
+ *                followed by 12 reserved words, the fp32 first moments of all segments in segment order, then their second
+ *                moments.  The bias corrections
+ *                1 - beta^t are formed from t in float64 and rounded once; nothing else is kept for them.
+ *                mst_logit_adam_init zeroes the block; mst_logit_adam_state_bytes returns 0 for a count outside [1, 2^20].
+ *   loss_terms   host array of 1..MST_OPT_MAX_TERMS device pointers to fp32 scalars
+ *   history_row  device, 1 + n_terms fp32: [0] the sum of the terms, added left to right in fp32 from zero, [1 + k] term k
+ * One step, per coordinate:  g = dp p (1 - p);  m += (1 - beta1)(g - m);  v = beta2 v + (1 - beta2) g^2;  t += 1;
+ * theta -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps);  p = sigmoid(theta).  If a loss term or an element of a
+ * gradient is not finite, the history row is still written and [3] advances, but no coordinate changes, t stays, and the first such
+ * iteration is recorded in [1], [2]: the caller reads them when the loop is over.  The step reads nothing from the host - the step
+ * count lives in the state - and the same arguments (but history_row) serve every iteration.  One workgroup, one launch per call on
+ * `stream`, deterministic, no host synchronisation; every buffer is written exactly up to its count.  Bad arguments (NULL theta /
+ * p / state / history_row, counts or numbers of segments / terms out of range, lr <= 0, a beta outside [0, 1), eps < 0) return
+ * non-zero before anything is launched. */
+#define MST_OPT_MAX_SEGMENTS 4
+#define MST_OPT_MAX_TERMS 8
+#define MST_OPT_STATUS_NONFINITE 1
+typedef struct mst_logit_adam_segment {
+    float* theta;
+    float* p;
+    const float* grad_p;
+    int64_t count;
+} mst_logit_adam_segment;
+size_t mst_logit_adam_state_bytes(int64_t n_params);
+int mst_logit_adam_init(const mst_logit_adam_segment* segments, int32_t n_segments, void* state, void* stream);
+int mst_logit_adam_step(const mst_logit_adam_segment* segments, int32_t n_segments, const float* const* loss_terms, int32_t n_terms,
+                        float* history_row, double lr, double beta1, double beta2, double eps, void* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
  * (:127-195) and the 24-band Bark spectrum of mid/side (:62-124; STFT 32768 / hop 8192 / Hann).
