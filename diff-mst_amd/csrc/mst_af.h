@@ -16,16 +16,19 @@ constexpr int kAfBands = 24;
 constexpr int64_t kAfTwM = 0, kAfTwN = 2 * kAfM, kAfWin = kAfTwN + 2 * (kAfM + 1), kAfTwH = kAfWin + kAfFft,
                   kAfTablesFloats = kAfTwH + 2 * kAfHalf;
 
+// One launch chain analyses `sets` signal sets of one length n: 2 = {pred, target} (the paired loss), 1 = pred alone (a feature
+// profile, and the prediction's side of the loss against a profile; `target` is then never read).  The rows of every buffer keep
+// the paired numbering below, so what follows the analysis (k_af_final, the backward) reads one layout.
 struct AfArgs {
     const float* pred;    // (bs, 2, n)
-    const float* target;  // (bs, 2, n)
+    const float* target;  // (bs, 2, n); sets == 2 only
     const float* tables;
     const float* fb;      // (kAfBins, 24) filterbank, row-major like the reference's (n_freqs, n_barks)
-    float* magpart;       // (4*bs, n_groups, kAfBins) partial sums of |X| over a strip of frames
+    float* magpart;       // (2*sets*bs, n_groups, kAfBins) partial sums of |X| over a strip of frames
     float* meanmag;       // (4*bs, kAfBins)
     float* bark;          // (4*bs, 24) log band energies; (4*bs, 24) linear band energies follow
     double* stats;        // (2*bs, 8) reduced statistics per (signal set, b), see k_af_stats / k_af_finish
-    float* statpart;      // partials of the above
+    float* statpart;      // (sets*bs, n_statblk, 8) partials of the above
     float* bandpart;      // (4*bs, kAfBinSlices, 24) partial band energies
     float* losses;        // 5 weighted loss scalars out
     float* coef;          // backward coefficients
@@ -33,11 +36,11 @@ struct AfArgs {
     float* grad_pred;     // (bs, 2, n)
     float* yframes;       // (2*bs, n_frames, kAfFft) windowed adjoint frames of the prediction's mid / side signals
     float weights[5];
-    int bs, n_frames, n_groups, n_statblk;
+    int bs, sets, n_frames, n_groups, n_statblk;
     int64_t n;
 };
 
-// signal index s in [0, 4*bs): which = s / bs (0 pred mid, 1 pred side, 2 target mid, 3 target side), b = s % bs
+// signal index s in [0, 2*sets*bs): which = s / bs (0 pred mid, 1 pred side, 2 target mid, 3 target side), b = s % bs
 __device__ __forceinline__ void af_signal(const AfArgs& a, int s, const float*& l, const float*& r, float& sign) {
     const int which = s / a.bs, b = s % a.bs;
     const float* base = (which < 2 ? a.pred : a.target) + (int64_t)b * 2 * a.n;
@@ -48,7 +51,7 @@ __device__ __forceinline__ void af_signal(const AfArgs& a, int s, const float*& 
 
 // mst_af2.hip
 constexpr int kAf2Slots = 512;  // co-resident 512-lane workgroups (64 KiB of LDS each: two per CU)
-void launch_af2_bark_fwd(const AfArgs& a, hipStream_t stream);  // grid (n_groups, 4 bs, 2 halves)
+void launch_af2_bark_fwd(const AfArgs& a, hipStream_t stream);  // grid (n_groups, 2 sets bs, 2 halves)
 void launch_af2_bark_bwd(const AfArgs& a, hipStream_t stream);  // grid (n_frames, 2 bs)
 
 }  // namespace mst

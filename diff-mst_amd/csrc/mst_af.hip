@@ -10,7 +10,7 @@
 
 namespace mst {
 
-// mean over frames + filterbank, one slice of the bins per workgroup.  grid (kAfBinSlices, 4*bs), 256 lanes.
+// mean over frames + filterbank, one slice of the bins per workgroup.  grid (kAfBinSlices, 2*sets*bs), 256 lanes.
 constexpr int kAfStatSpan = 256 * 16;  // samples per k_af_stats workgroup
 constexpr int kAfBinSlices = 16;
 constexpr int kAfSliceBins = (kAfBins + kAfBinSlices - 1) / kAfBinSlices;
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(256) void k_af_bark_reduce(AfArgs a) {
     if (tid < kAfBands)
         a.bandpart[((int64_t)s * kAfBinSlices + sl) * kAfBands + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
-// slices -> band energies (log and linear) of signal s, and the statistics of (set, b) = blockIdx.x < 2*bs.
-// grid (4*bs), 64 lanes: fixed-order sums.
+// slices -> band energies (log and linear) of signal s, and the statistics of (set, b) = blockIdx.x < sets*bs.
+// grid (2*sets*bs), 64 lanes: fixed-order sums.
 __global__ __launch_bounds__(64) void k_af_finish(AfArgs a) {
     const int tid = threadIdx.x, s = blockIdx.x;
     if (tid < kAfBands) {
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(64) void k_af_finish(AfArgs a) {
         a.bark[(int64_t)s * kAfBands + tid] = logf(lin + 1e-8f);
         a.bark[(int64_t)(4 * a.bs + s) * kAfBands + tid] = lin;
     }
-    if (s < 2 * a.bs) {  // statistics of signal set / batch item sb = s: lanes stride over the time blocks
+    if (s < a.sets * a.bs) {  // statistics of signal set / batch item sb = s: lanes stride over the time blocks
         double sum[4] = {0, 0, 0, 0};
         float ml = -1.f, mr = -1.f;
         int64_t il = 0x7fffffffffffLL, ir = 0x7fffffffffffLL;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(64) void k_af_finish(AfArgs a) {
     }
 }
 
-// ---- closed-form features: per (set in {pred,target}, b) partial reductions over a slice of time
+// ---- closed-form features: per (set in {pred,target}, b) partial reductions over a slice of time.  grid (n_statblk, sets*bs)
 // stat slots: 0 sum L^2, 1 sum R^2, 2 sum (L+R)^2, 3 sum (L-R)^2, 4 max|L|, 5 argmax L, 6 max|R|, 7 argmax R
 __global__ __launch_bounds__(256) void k_af_stats(AfArgs a) {
     __shared__ float sv[4][8];
@@ -228,6 +228,32 @@ __global__ __launch_bounds__(64) void k_af_coef(AfArgs a) {
     for (int b = threadIdx.x; b < a.bs; b += 64) af_features(a, b, a.grad_losses, part, a.coef + (int64_t)b * 16);
 }
 
+// ---- feature profile (include/diffmst_hip.h: MST_AF_PROFILE_DOUBLES) ----------------------------------
+// What k_af_final, k_af_coef and k_af_bark_dmag read of the target is stats rows bs..2bs-1 (slots 0..4 and 6; the target's arg-max
+// slots 5 and 7 are never used) and the log band energies in bark rows 2bs..4bs-1: 54 numbers per batch item.  pack copies them out
+// of a one-set analysis (where they sit in the prediction's rows), unpack puts a profile into the target's rows.  grid (bs), 64 lanes.
+constexpr int kAfProfile = 6 + 2 * kAfBands;
+__global__ __launch_bounds__(64) void k_af_profile_pack(AfArgs a, double* profile) {
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (tid >= kAfProfile) return;
+    double v;
+    if (tid < 4) v = a.stats[(int64_t)b * 8 + tid];
+    else if (tid < 6) v = a.stats[(int64_t)b * 8 + 4 + 2 * (tid - 4)];  // max|L|, max|R|
+    else if (tid < 6 + kAfBands) v = (double)a.bark[(int64_t)b * kAfBands + (tid - 6)];  // mid
+    else v = (double)a.bark[(int64_t)(a.bs + b) * kAfBands + (tid - 6 - kAfBands)];      // side
+    profile[(int64_t)b * kAfProfile + tid] = v;
+}
+__global__ __launch_bounds__(64) void k_af_profile_unpack(AfArgs a, const double* profile) {
+    const int tid = threadIdx.x, b = blockIdx.x;
+    if (tid >= kAfProfile) return;
+    const double v = profile[(int64_t)b * kAfProfile + tid];
+    double* st = a.stats + (int64_t)(a.bs + b) * 8;
+    if (tid < 4) st[tid] = v;
+    else if (tid < 6) { st[4 + 2 * (tid - 4)] = v; st[5 + 2 * (tid - 4)] = 0.0; }
+    else if (tid < 6 + kAfBands) a.bark[(int64_t)(2 * a.bs + b) * kAfBands + (tid - 6)] = (float)v;
+    else a.bark[(int64_t)(3 * a.bs + b) * kAfBands + (tid - 6 - kAfBands)] = (float)v;
+}
+
 // ---- backward ---------------------------------------------------------------------------------------
 // dM[s][k] = sum_j (w4 * 2 (B - Bt) / (2 bs 24)) / (lin_j + 1e-8) * fb[k][j] / F   for the 2*bs prediction signals
 __global__ __launch_bounds__(256) void k_af_bark_dmag(AfArgs a) {
@@ -366,23 +392,25 @@ static int af_groups(int n_frames, int n_signals) {
     }
     return best;
 }
-static AfPlan af_plan(int bs, int64_t n) {
+// sets = 2: the paired loss; sets = 1: one signal set with its own n and its own strip plan (4*bs (signal, half) units, not 8*bs).
+// The rows the analysis does not fill (magpart, statpart) are not allocated; everything read after it keeps the paired layout.
+static AfPlan af_plan(int bs, int64_t n, int sets = 2, bool backward = true) {
     AfPlan p{};
     p.ok = bs > 0 && n > kAfFft / 2;
     if (!p.ok) return p;
     p.n_frames = 1 + (int)(n / kAfHop);
-    p.n_groups = af_groups(p.n_frames, 8 * bs);
+    p.n_groups = af_groups(p.n_frames, 4 * sets * bs);
     p.n_statblk = (int)((n + kAfStatSpan - 1) / kAfStatSpan);
     int64_t o = 0;
     auto take = [&](int64_t k) { int64_t at = o; o += round_up(k, 64); return at; };
-    p.magpart = take((int64_t)4 * bs * p.n_groups * kAfBins);
+    p.magpart = take((int64_t)2 * sets * bs * p.n_groups * kAfBins);
     p.meanmag = take((int64_t)6 * bs * kAfBins);  // 4*bs mean magnitudes + 2*bs bark cotangents
     p.bark = take((int64_t)8 * bs * kAfBands);    // log energies, then linear energies
-    p.statpart = take((int64_t)2 * bs * p.n_statblk * 8);
+    p.statpart = take((int64_t)sets * bs * p.n_statblk * 8);
     p.bandpart = take((int64_t)4 * bs * kAfBinSlices * kAfBands);
     p.stats = take((int64_t)2 * bs * 8 * 2);  // doubles
     p.coef = take((int64_t)bs * 16);
-    p.yframes = take((int64_t)2 * bs * p.n_frames * kAfFft);  // backward only
+    p.yframes = take(backward ? (int64_t)2 * bs * p.n_frames * kAfFft : 0);  // backward only
     p.total = o;
     return p;
 }
@@ -395,8 +423,22 @@ static AfArgs af_args(const AfPlan& p, int bs, int64_t n, const float* pred, con
     a.yframes = ws + p.yframes;
     a.bandpart = ws + p.bandpart; a.stats = reinterpret_cast<double*>(ws + p.stats);
     for (int i = 0; i < 5; ++i) a.weights[i] = weights[i];
-    a.bs = bs; a.n_frames = p.n_frames; a.n_groups = p.n_groups; a.n_statblk = p.n_statblk; a.n = n;
+    a.bs = bs; a.sets = target ? 2 : 1; a.n_frames = p.n_frames; a.n_groups = p.n_groups; a.n_statblk = p.n_statblk; a.n = n;
     return a;
+}
+// statistics and band energies of a.sets signal sets into `stats` and `bark`
+static void af_analyse(const AfArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_af_stats, dim3(a.n_statblk, a.sets * a.bs), dim3(256), 0, stream, a);
+    launch_af2_bark_fwd(a, stream);
+    hipLaunchKernelGGL(k_af_bark_reduce, dim3(kAfBinSlices, 2 * a.sets * a.bs), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_af_finish, dim3(2 * a.sets * a.bs), dim3(64), 0, stream, a);
+}
+// the four launches that turn the forward's workspace and the upstream gradients into grad_pred
+static void af_backward(const AfArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(k_af_coef, dim3(1), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(k_af_bark_dmag, dim3((kAfBins + 255) / 256, 2 * a.bs), dim3(256), 0, stream, a);
+    launch_af2_bark_bwd(a, stream);
+    hipLaunchKernelGGL(k_af_bwd_gather, dim3((unsigned)((a.n + 1023) / 1024), a.bs), dim3(256), 0, stream, a);
 }
 }  // namespace mst
 
@@ -421,10 +463,7 @@ extern "C" int mst_afloss_forward(const float* pred, const float* target, int32_
     hipStream_t stream = (hipStream_t)stream_;
     AfArgs a = af_args(p, bs, n_samples, pred, target, (const float*)tables, filterbank, weights5, (float*)workspace);
     a.losses = losses5;
-    hipLaunchKernelGGL(k_af_stats, dim3(p.n_statblk, 2 * bs), dim3(256), 0, stream, a);
-    launch_af2_bark_fwd(a, stream);
-    hipLaunchKernelGGL(k_af_bark_reduce, dim3(kAfBinSlices, 4 * bs), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(k_af_finish, dim3(4 * bs), dim3(64), 0, stream, a);
+    af_analyse(a, stream);
     hipLaunchKernelGGL(k_af_final, dim3(1), dim3(64), 0, stream, a);
     return (int)hipGetLastError();
 }
@@ -439,9 +478,58 @@ extern "C" int mst_afloss_backward(const float* pred, const float* target, int32
     AfArgs a = af_args(p, bs, n_samples, pred, target, (const float*)tables, filterbank, weights5, (float*)workspace);
     a.grad_losses = grad_losses5;
     a.grad_pred = grad_pred;
-    hipLaunchKernelGGL(k_af_coef, dim3(1), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(k_af_bark_dmag, dim3((kAfBins + 255) / 256, 2 * bs), dim3(256), 0, stream, a);
-    launch_af2_bark_bwd(a, stream);
-    hipLaunchKernelGGL(k_af_bwd_gather, dim3((unsigned)((n_samples + 1023) / 1024), bs), dim3(256), 0, stream, a);
+    af_backward(a, stream);
+    return (int)hipGetLastError();
+}
+
+// ---- feature profiles (ABI v13): the target analysed once, the loss and its backward against the 54 numbers it leaves ------------
+static_assert(kAfProfile == MST_AF_PROFILE_DOUBLES, "profile row");
+extern "C" size_t mst_af_profile_workspace_bytes(int32_t bs, int64_t n_samples) {
+    const AfPlan p = af_plan(bs, n_samples, 1, false);
+    return p.ok ? (size_t)p.total * sizeof(float) : 0;
+}
+extern "C" int mst_af_profile(const float* x, int32_t bs, int64_t n_samples, const void* tables, const float* filterbank,
+                              double* profile, void* workspace, size_t workspace_bytes, void* stream_) {
+    const AfPlan p = af_plan(bs, n_samples, 1, false);
+    if (!p.ok || !x || !tables || !filterbank || !profile || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    const float no_weights[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    const AfArgs a = af_args(p, bs, n_samples, x, nullptr, (const float*)tables, filterbank, no_weights, (float*)workspace);
+    af_analyse(a, stream);
+    hipLaunchKernelGGL(k_af_profile_pack, dim3(bs), dim3(64), 0, stream, a, profile);
+    return (int)hipGetLastError();
+}
+extern "C" size_t mst_afloss_profile_workspace_bytes(int32_t bs, int64_t n_samples) {
+    const AfPlan p = af_plan(bs, n_samples, 1);
+    return p.ok ? (size_t)p.total * sizeof(float) : 0;
+}
+extern "C" int mst_afloss_forward_profile(const float* pred, const double* profile, int32_t bs, int64_t n_samples,
+                                          const float* weights5, const void* tables, const float* filterbank, float* losses5,
+                                          void* workspace, size_t workspace_bytes, void* stream_) {
+    const AfPlan p = af_plan(bs, n_samples, 1);
+    if (!p.ok || !pred || !profile || !weights5 || !tables || !filterbank || !losses5 || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    AfArgs a = af_args(p, bs, n_samples, pred, nullptr, (const float*)tables, filterbank, weights5, (float*)workspace);
+    a.losses = losses5;
+    af_analyse(a, stream);
+    hipLaunchKernelGGL(k_af_profile_unpack, dim3(bs), dim3(64), 0, stream, a, profile);
+    hipLaunchKernelGGL(k_af_final, dim3(1), dim3(64), 0, stream, a);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_afloss_backward_profile(const float* pred, const double* profile, int32_t bs, int64_t n_samples,
+                                           const float* weights5, const void* tables, const float* filterbank,
+                                           const float* grad_losses5, float* grad_pred, void* workspace, size_t workspace_bytes,
+                                           void* stream_) {
+    const AfPlan p = af_plan(bs, n_samples, 1);
+    if (!p.ok || !pred || !profile || !weights5 || !tables || !filterbank || !grad_losses5 || !grad_pred || !workspace)
+        return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    AfArgs a = af_args(p, bs, n_samples, pred, nullptr, (const float*)tables, filterbank, weights5, (float*)workspace);
+    a.grad_losses = grad_losses5;
+    a.grad_pred = grad_pred;
+    af_backward(a, stream);  // reads what mst_afloss_forward_profile left in the workspace, the unpacked profile included
     return (int)hipGetLastError();
 }

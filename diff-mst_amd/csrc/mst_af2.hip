@@ -165,9 +165,9 @@ __global__ __launch_bounds__(kAf2Lanes, MST_AF2_W) void k_af2_bark_fwd(AfArgs a)
     // the four sat on four XCDs - every frame (256 KB) crossed the fabric four times, 2.2 GB per launch at bs 32, against an L2 that
     // 64 resident workgroups x 256 KB overflow anyway.  Any other batch size keeps the plain walk; the result does not depend on it.
     int grp = blockIdx.x, sgn = blockIdx.y, half = blockIdx.z;
-    if ((2 * a.bs) % 8 == 0) {
+    if ((a.sets * a.bs) % 8 == 0) {
         const int L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), xcd = L & 7, k = L >> 3;
-        const int W = 4 * a.n_groups, src = (k / W) * 8 + xcd, rem = k % W, var = rem & 3;  // src = (pred | target, batch item)
+        const int W = 4 * a.n_groups, src = (k / W) * 8 + xcd, rem = k % W, var = rem & 3;  // src = (set, batch item) < sets*bs
         grp = rem >> 2;
         half = var >> 1;
         sgn = (2 * (src / a.bs) + (var & 1)) * a.bs + src % a.bs;
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kAf2Lanes, MST_AF2_W_BWD) void k_af2_bark_bwd(AfArg
 }
 
 void launch_af2_bark_fwd(const AfArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(k_af2_bark_fwd, dim3(a.n_groups, 4 * a.bs, 2), dim3(kAf2Lanes), 0, stream, a);
+    hipLaunchKernelGGL(k_af2_bark_fwd, dim3(a.n_groups, 2 * a.sets * a.bs, 2), dim3(kAf2Lanes), 0, stream, a);
 }
 void launch_af2_bark_bwd(const AfArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_af2_bark_bwd<0>), dim3(a.n_frames, 2 * a.bs), dim3(kAf2Lanes), 0, stream, a);

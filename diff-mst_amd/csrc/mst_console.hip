@@ -21,7 +21,7 @@ static int check_desc(const mst_console_desc* d) {
 
 using namespace mst;
 
-extern "C" int mst_abi_version(void) { return 12; }
+extern "C" int mst_abi_version(void) { return 13; }
 MST_DEV_PROBE_STATE  // developer probe, mst_dev.h (nothing in a default build)
 
 extern "C" size_t mst_console_fx_tables_bytes(void) { return (size_t)8192 * 2 * sizeof(float); }

@@ -25,7 +25,7 @@ NO_RANGE_CHECK = 0x400
 BWD_PREPARED = 0x800
 SPLIT_BATCH = 0x1000
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class ConsoleDesc(C.Structure):
@@ -119,6 +119,7 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
 
 
 OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
+AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
 
 
 class LogitAdamSegment(C.Structure):  # mirrors mst_logit_adam_segment
@@ -219,6 +220,11 @@ SIGNATURES = {
     "mst_cnn14_backward_sync": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, C.POINTER(Cnn14Grads), _P, C.c_size_t, _S,
                                         SYNC_FN, _S]),
     "mst_afloss_backward": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_af_profile_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "mst_af_profile": (STATUS, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_afloss_profile_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "mst_afloss_forward_profile": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_afloss_backward_profile": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_ctrl_workspace_bytes": (C.c_size_t, [C.POINTER(CtrlDesc)]),
     "mst_ctrl_forward": (STATUS, [C.POINTER(CtrlDesc), _P, _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),
     "mst_ctrl_backward": (STATUS, [C.POINTER(CtrlDesc), _P, C.POINTER(CtrlLayer), _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),

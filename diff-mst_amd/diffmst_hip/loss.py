@@ -224,12 +224,108 @@ class _AudioFeatureFunction(torch.autograd.Function):
         return gx.view(shape), None, None, None
 
 
+class AudioFeatureProfile:
+    """The five features of a stereo signal as ``AudioFeatureLoss`` compares them: what is left of a target once it has been analysed.
+
+    ``data`` is a ``(bs, 54)`` float64 device tensor in the layout ``include/diffmst_hip.h`` documents (``MST_AF_PROFILE_DOUBLES``):
+    mean L^2, R^2, (L+R)^2, (L-R)^2; max|L|, max|R|; the 24 log Bark band energies of the mid signal, then of the side signal.  None
+    of it depends on the length of the signal, so a profile stands in for a target of any length; ``n_samples`` only records what was
+    analysed (``None`` for a profile rebuilt from stored ``data``: ``AudioFeatureProfile(data, sample_rate)`` reloads one).
+
+    ``rms``, ``crest_factor``, ``stereo_width``, ``stereo_imbalance`` and ``barkspectrum`` are the values the reference's
+    ``compute_rms`` ... ``compute_barkspectrum`` (mst/loss.py:62-195) return for that audio, in its shapes and as float32: a few torch
+    operations on the 54 numbers, for reports.  They carry no gradient.
+    """
+
+    def __init__(self, data: torch.Tensor, sample_rate: int, n_samples: int = None) -> None:
+        if not isinstance(data, torch.Tensor) or data.dim() != 2 or data.shape[1] != _cabi.AF_PROFILE_DOUBLES or data.dtype != torch.float64:
+            raise ValueError(f"a profile is a (bs, {_cabi.AF_PROFILE_DOUBLES}) float64 tensor")
+        self.data = data.detach().contiguous()
+        self.sample_rate = sample_rate
+        self.n_samples = None if n_samples is None else int(n_samples)
+
+    @property
+    def batch_size(self) -> int:
+        return self.data.shape[0]
+
+    def to(self, device) -> "AudioFeatureProfile":
+        return AudioFeatureProfile(self.data.to(device), self.sample_rate, self.n_samples)
+
+    @property
+    def rms(self) -> torch.Tensor:  # (bs, 2)
+        return self.data[:, 0:2].clamp(min=1e-8).sqrt().float()
+
+    @property
+    def crest_factor(self) -> torch.Tensor:  # (bs, 2), dB
+        rms = self.data[:, 0:2].clamp(min=1e-8).sqrt()
+        return (20.0 * torch.log10((self.data[:, 4:6] / rms.clamp(min=1e-8)).clamp(min=1e-8))).float()
+
+    @property
+    def stereo_width(self) -> torch.Tensor:  # (bs,)
+        return (self.data[:, 3] / self.data[:, 2].clamp(min=1e-8)).float()
+
+    @property
+    def stereo_imbalance(self) -> torch.Tensor:  # (bs,)
+        el, er = self.data[:, 0], self.data[:, 1]
+        return ((er - el) / (er + el).clamp(min=1e-8)).float()
+
+    @property
+    def barkspectrum(self) -> torch.Tensor:  # (bs, 24, 2): [..., 0] mid, [..., 1] side
+        return torch.stack((self.data[:, 6:30], self.data[:, 30:54]), dim=-1).float()
+
+
+def _af_check_input(x, what):
+    if x.dim() != 3 or x.shape[1] != 2:
+        raise ValueError(f"AudioFeatureLoss expects a (bs, 2, seq_len) {what}, got {tuple(x.shape)}")
+
+
+class _AudioFeatureProfileFunction(torch.autograd.Function):
+    """The loss of ``pred`` against a profile: the prediction's half of ``_AudioFeatureFunction``'s work."""
+
+    @staticmethod
+    def forward(ctx, pred, profile, weights, sample_rate):
+        lib = _hip.lib()
+        x = pred.float().contiguous()
+        bs, _, n = x.shape
+        dev = x.device
+        tables, fb = _af_constants(dev, sample_rate)
+        nbytes = lib.mst_afloss_profile_workspace_bytes(bs, n)
+        if nbytes == 0:
+            raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        losses = torch.empty(5, dtype=torch.float32, device=dev)
+        w = (ctypes.c_float * 5)(*[float(v) for v in weights])
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_forward_profile(x, profile, bs, n, w, tables, fb, losses, ws, nbytes, st)
+        ctx.meta = (bs, n, w, nbytes, pred.shape)
+        ctx.save_for_backward(x, profile, tables, fb, ws)
+        return tuple(losses.unbind(0))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_each):
+        x, profile, tables, fb, ws = ctx.saved_tensors
+        bs, n, w, nbytes, shape = ctx.meta
+        lib = _hip.lib()
+        dev = x.device
+        g = torch.stack([gi.float().reshape(()) for gi in grad_each]).contiguous()
+        gx = torch.empty_like(x)
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_backward_profile(x, profile, bs, n, w, tables, fb, g, gx, ws, nbytes, st)
+        return gx.view(shape), None, None, None
+
+
 class AudioFeatureLoss(torch.nn.Module):
     """Drop-in for reference ``mst.loss.AudioFeatureLoss`` (:198-260).
 
     ``forward(input, target)`` returns ``{key: weight * mse(feature(input), feature(target))}`` with the
     reference's five keys (``System`` sums ``val.mean()`` over them, mst/system.py:334-336).  All five
     features and their gradients are computed by the kernels of ``csrc/mst_af.hip`` in one pass.
+
+    The features are aggregates over time, so - as in the reference - the target need not have the input's length: a ``(bs, 2, m)``
+    target with ``m != seq_len`` is analysed into an ``AudioFeatureProfile`` and the loss runs against that; ``profile(x)`` returns
+    the profile itself, to be passed as ``target`` wherever one target meets many inputs (``mst.online.optimize``): the target's
+    transforms then run once instead of in every call.  A target of the input's shape takes the paired kernels, as it always has.
     """
 
     def __init__(self, weights: List[float], sample_rate: int, stem_separation: bool = False, use_clap: bool = False) -> None:
@@ -243,6 +339,46 @@ class AudioFeatureLoss(torch.nn.Module):
         self.transform_names = ["rms", "crest_factor", "stereo_width", "stereo_imbalance", "barkspectrum"]
         assert len(self.transform_names) == len(weights)
 
-    def forward(self, input: torch.Tensor, target: torch.Tensor):
-        losses = _AudioFeatureFunction.apply(input, target, tuple(self.weights), self.sample_rate)
+    Profile = AudioFeatureProfile  # reachable wherever this class is: ``mst.loss.AudioFeatureLoss.Profile`` after ``install()``
+
+    @torch.no_grad()
+    def profile(self, x: torch.Tensor) -> AudioFeatureProfile:
+        """Analyse ``x (bs, 2, n)``, ``n > 16384``, on its device -> ``AudioFeatureProfile``.  No gradient reaches ``x``: the target
+        side of this loss never receives one."""
+        _hip.require_cuda(x)
+        _af_check_input(x, "signal")
+        lib = _hip.lib()
+        x = x.detach().float().contiguous()
+        bs, _, n = x.shape
+        dev = x.device
+        nbytes = lib.mst_af_profile_workspace_bytes(bs, n)
+        if nbytes == 0:
+            raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
+        tables, fb = _af_constants(dev, self.sample_rate)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        data = torch.empty(bs, _cabi.AF_PROFILE_DOUBLES, dtype=torch.float64, device=dev)
+        with _hip.launch_on(dev) as st:
+            lib.mst_af_profile(x, bs, n, tables, fb, data, ws, nbytes, st)
+        return AudioFeatureProfile(data, self.sample_rate, n)
+
+    def forward(self, input: torch.Tensor, target):
+        if isinstance(target, torch.Tensor) and target.shape == input.shape:
+            losses = _AudioFeatureFunction.apply(input, target, tuple(self.weights), self.sample_rate)
+            return dict(zip(AF_KEYS, losses))
+        is_profile = isinstance(target, AudioFeatureProfile)
+        if not is_profile and not isinstance(target, torch.Tensor):
+            raise TypeError(f"AudioFeatureLoss takes a tensor or an AudioFeatureProfile as target, got {type(target).__name__}")
+        _hip.require_cuda(input, target.data if is_profile else target)
+        _af_check_input(input, "input")
+        if is_profile:
+            if target.sample_rate != self.sample_rate:
+                raise ValueError(f"the profile was taken at {target.sample_rate} Hz, this loss runs at {self.sample_rate} Hz")
+        else:
+            _af_check_input(target, "target")
+        if (target.batch_size if is_profile else target.shape[0]) != input.shape[0]:
+            raise ValueError(f"input has batch size {input.shape[0]}, the target {target.batch_size if is_profile else target.shape[0]}")
+        if not is_profile:
+            target = self.profile(target)  # another length: the reference takes it (its features are means and maxima over time)
+        _hip.require_same_device(input.device, target.data)
+        losses = _AudioFeatureProfileFunction.apply(input, target.data, tuple(self.weights), self.sample_rate)
         return dict(zip(AF_KEYS, losses))

@@ -18,6 +18,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _cabi, _hip
+from .loss import AudioFeatureProfile
 
 
 def start_point(n_tracks: int, mix_console, init_scale: float = 0.001, generator=None):
@@ -55,19 +56,32 @@ class _Run:
     ``finish()`` (the one read of history and status)."""
 
     def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags):
-        _hip.require_cuda(tracks, ref_mix)
+        is_profile = isinstance(ref_mix, AudioFeatureProfile)
+        if not is_profile and not isinstance(ref_mix, torch.Tensor):
+            raise TypeError(f"ref_mix must be a (2, n_samples) tensor or an AudioFeatureProfile, got {type(ref_mix).__name__}")
+        _hip.require_cuda(tracks, ref_mix.data if is_profile else ref_mix)
         if tracks.dim() != 2:
             raise ValueError(f"tracks must be (n_tracks, n_samples), got {tuple(tracks.shape)} (one song per call: no batch dimension)")
-        if ref_mix.dim() != 2 or ref_mix.shape[0] != 2 or ref_mix.shape[1] != tracks.shape[1]:
-            raise ValueError(f"ref_mix must be (2, {tracks.shape[1]}), got {tuple(ref_mix.shape)}")
-        _hip.require_same_device(tracks.device, ref_mix)
+        if is_profile:
+            if ref_mix.batch_size != 1:
+                raise ValueError(f"a profile given as ref_mix must have batch size 1, got {ref_mix.batch_size}")
+        elif ref_mix.dim() != 2 or ref_mix.shape[0] != 2:
+            raise ValueError(f"ref_mix must be (2, n_samples) or an AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+        _hip.require_same_device(tracks.device, ref_mix.data if is_profile else ref_mix)
         if int(n_iters) < 1:
             raise ValueError("n_iters must be at least 1")
         dev = tracks.device
         self.console, self.loss_function, self.callback = mix_console, loss_function, callback
         self.flags = dict(use_fx_bus=False)
         self.flags.update(console_flags)
-        self.tracks, self.ref_mix = tracks.detach().unsqueeze(0), ref_mix.detach().unsqueeze(0)
+        self.tracks = tracks.detach().unsqueeze(0)
+        if is_profile:
+            self.ref_mix = ref_mix
+        else:
+            self.ref_mix = ref_mix.detach().unsqueeze(0)
+            if ref_mix.shape[1] != tracks.shape[1] and hasattr(loss_function, "profile"):
+                # a reference of another length (the usual case: it is another song) is analysed here, once; the loop gets the profile
+                self.ref_mix = loss_function.profile(self.ref_mix)
         self.n_iters = int(n_iters)
         self.hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps))
         start = start_point(tracks.shape[0], mix_console, init_scale, generator)
@@ -122,11 +136,21 @@ def optimize(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1
              generator=None, callback=None, **console_flags):
     """The reference's ``optimize`` (scripts/online.py:15-123): fit the console's parameters to ``ref_mix`` by Adam on their logits.
 
-    ``tracks (T, N)`` and ``ref_mix (2, N)`` are device tensors (a CPU tensor raises, as everywhere in this package).  Every iteration
+    ``tracks (T, N)`` and ``ref_mix (2, M)`` are device tensors (a CPU tensor raises, as everywhere in this package).  Every iteration
     calls ``mix_console(tracks[None], p_tracks, p_fx, p_master, use_fx_bus=False, **console_flags)`` with ``p = sigmoid(logits)`` and
-    ``loss_function(mix, ref_mix[None])`` - a dictionary of one-element terms, summed in its order like the script's ``loss += value``,
+    ``loss_function(mix, target)`` - a dictionary of one-element terms, summed in its order like the script's ``loss += value``,
     or a single tensor - takes ``torch.autograd.grad`` of the terms with respect to the three ``p`` and hands the rest to one kernel
-    launch.  Returns the script's 8-tuple
+    launch.
+
+    The ``target`` of every iteration: with ``M == N`` it is ``ref_mix[None]``.  With ``M != N`` (the reference mix is another song: the
+    script's own ``ref_mix[:, start:start + block]`` comes out shorter whenever that song ends early) and a ``loss_function`` that has a
+    ``profile`` method (``AudioFeatureLoss``), ``loss_function.profile(ref_mix[None])`` is taken once, before the first iteration,
+    and every iteration gets that ``AudioFeatureProfile``; any other loss function is handed ``ref_mix[None]`` as it is and decides
+    itself.  ``ref_mix`` may also BE an ``AudioFeatureProfile`` of batch size 1 - a stored one, or ``loss_function.profile(ref_mix[None])``
+    of an equal-length reference (``profile`` takes ``(bs, 2, n)``), which spares the loop the target's half of the loss forward (an
+    equal-length tensor keeps the paired kernels, as it always has).
+
+    Returns the script's 8-tuple
 
         ``(mix, track_logits, track_param_dict, fx_bus_logits, fx_bus_param_dict, master_bus_logits, master_bus_param_dict, loss_history)``
 

@@ -373,6 +373,39 @@ int mst_afloss_backward(const float* pred, const float* target, int32_t bs, int6
                         const void* tables, const float* filterbank, const float* grad_losses5, float* grad_pred,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Feature profiles (ABI v13): none of the five features depends on the length of the signal, so the target may be ANALYSED ONCE into
+ * 54 float64 numbers per batch item and the loss and its backward then run against those instead of against audio - the target may
+ * have any length > 16384 (the reference accepts unequal lengths, mst/loss.py:127-260), it need not stay resident, and a loop against
+ * one fixed target transforms 2 bs signals per forward instead of 4 bs.
+ *
+ * Layout of a profile row (MST_AF_PROFILE_DOUBLES doubles; fixed: stored profiles stay readable, a later quantity is appended under
+ * a new count).  The length of the analysed signal is NOT part of it.
+ *   [0..3]    mean L^2, mean R^2, mean (L+R)^2, mean (L-R)^2   float64 sums of fp32 block sums, divided by n
+ *   [4..5]    max |L|, max |R|
+ *   [6..29]   log(band energy + 1e-8) of the 24 Bark bands of the mid signal L+R   (fp32 values, widened)
+ *   [30..53]  the same of the side signal L-R
+ * From these: rms = sqrt(max([0..1], 1e-8)); crest factor = 20 log10([4..5] / rms); width = [3] / max([2], 1e-8);
+ * imbalance = ([1] - [0]) / max([1] + [0], 1e-8); Bark spectrum [b][band][mid|side].
+ *
+ *   mst_af_profile              x (bs, 2, n_samples) -> profile (bs, 54); exactly bs*54 doubles are written
+ *   mst_afloss_forward_profile  the five weighted losses of pred (bs, 2, n_samples) against profile (bs, 54)
+ *   mst_afloss_backward_profile grad_pred of that call; same workspace, after the forward, as mst_afloss_backward
+ * pred is analysed by the arithmetic mst_af_profile uses (same strip plan at the same bs and n_samples): the loss of a signal against
+ * its own profile is exactly 0.  mst_afloss_forward / _backward above are unchanged and bit-identical to ABI v12.  Fixed-order sums,
+ * no float atomics: bitwise reproducible.  n_samples <= 16384, bs <= 0, a NULL pointer or a workspace that is too small return
+ * non-zero before anything is launched; the *_workspace_bytes functions return 0 for such bs / n_samples. */
+#define MST_AF_PROFILE_DOUBLES 54
+size_t mst_af_profile_workspace_bytes(int32_t bs, int64_t n_samples);
+int mst_af_profile(const float* x, int32_t bs, int64_t n_samples, const void* tables, const float* filterbank, double* profile,
+                   void* workspace, size_t workspace_bytes, void* stream);
+size_t mst_afloss_profile_workspace_bytes(int32_t bs, int64_t n_samples);
+int mst_afloss_forward_profile(const float* pred, const double* profile, int32_t bs, int64_t n_samples, const float* weights5,
+                               const void* tables, const float* filterbank, float* losses5, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int mst_afloss_backward_profile(const float* pred, const double* profile, int32_t bs, int64_t n_samples, const float* weights5,
+                                const void* tables, const float* filterbank, const float* grad_losses5, float* grad_pred,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Spectrogram encoder: SpectrogramEncoder (reference mst/modules.py:740-806) = STFT front end +
  * Cnn14 (mst/panns.py:126-209, ConvBlock :27-85).  The 3x3 convolutions run on the matrix cores (MFMA); activations are
