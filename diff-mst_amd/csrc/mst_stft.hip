@@ -1,7 +1,7 @@
 // mst_stft.hip - multi-resolution STFT loss (auraloss 0.4.0 semantics; reference
 // configuration configs/models/naive.yaml:54-68, call site mst/system.py:331).
 //
-//   per resolution: frames of torch.stft(center=True, reflect pad, periodic Hann), hop = n_fft/2..n_fft/4
+//   per resolution: frames of torch.stft(center=True, reflect pad, periodic Hann), any positive hop (beyond n_fft too)
 //   mag = sqrt(max(re^2+im^2, 1e-8));  SC = ||ym - xm||_F / ||ym||_F (per row or global);
 //   logmag = mean |log xm - log ym|;  loss = mean over resolutions of w_sc SC + w_log logmag + w_lin L1.
 //
@@ -523,9 +523,9 @@ __global__ void k_stft_tables(float* tables, ResInfo r, int win_length) {
     const int off = (r.n_fft - win_length) / 2;
     float w = 0.0f;
     if (t >= off && t < off + win_length) {
-        // torch.hann_window(win_length) (periodic), evaluated in fp32 like torch does
+        // torch.hann_window(win_length) (periodic), evaluated in fp32 like torch does; a one-point window is [1], not the formula's 0
         const float ph = 6.283185307179586f * (float)(t - off) / (float)win_length;
-        w = 0.5f - 0.5f * (float)cos((double)ph);
+        w = win_length == 1 ? 1.0f : 0.5f - 0.5f * (float)cos((double)ph);
     }
     tables[r.win_off + t] = w;
 }
@@ -616,6 +616,7 @@ Plan make_plan(const mst_mrstft_desc* d) {
     p.ok = false;
     if (!d || d->rows <= 0 || d->n_res <= 0 || d->n_res > kMaxRes) return p;
     int64_t t = 0, po = 0;
+    bool have_seam = false;  // a seam-mode resolution already runs on the round-2 kernels
     for (int i = 0; i < d->n_res; ++i) {
         const int nf = d->fft_size[i];
         int lg = 0;
@@ -641,6 +642,12 @@ Plan make_plan(const mst_mrstft_desc* d) {
         // that no frame reflects at both ends, whole hops per row (the owner-computes overlap-add assumes it)
         p.engine2[i] = (nf == 512 || nf == 2048 || nf == 8192) && r.hop * 2 == nf && d->win_length[i] == nf &&
                        d->n_samples >= 2 * (int64_t)nf && d->n_samples % r.hop == 0;
+        // ... and at most ONE seam-mode (8192-point) resolution: a seam-mode backward launch stores its blocks, it does not add to what an
+        // earlier one stored.  A second one takes the generic kernels, and with it the whole backward does (mst_mrstft_backward).
+        if (p.engine2[i] && stft2_bwd_needs_zero(nf)) {
+            if (have_seam) p.engine2[i] = false;
+            have_seam = true;
+        }
         if (p.engine2[i]) {
             // balanced strips of ~8 / 4 / 2 frames (one workgroup each): consecutive frames share half their samples
             // fused forward with the kept spectra (one box, us): (4, 4) 83.8; (3, 4) 80.0; (3, 6) 79.6; (3, 7) 80.0; (4, 6) 78.6 vs 81.5; (6, 4) 83.6 vs

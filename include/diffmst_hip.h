@@ -201,8 +201,8 @@ typedef struct mst_mrstft_desc {
     int64_t n_samples;
     int32_t n_res;
     int32_t fft_size[MST_MAX_RESOLUTIONS];   /* powers of two, 128..8192 */
-    int32_t hop_size[MST_MAX_RESOLUTIONS];
-    int32_t win_length[MST_MAX_RESOLUTIONS]; /* periodic Hann, centre-padded to fft_size */
+    int32_t hop_size[MST_MAX_RESOLUTIONS];   /* any positive hop, beyond fft_size too */
+    int32_t win_length[MST_MAX_RESOLUTIONS]; /* 1..fft_size; periodic Hann (a one-point window is [1]), centre-padded to fft_size */
     float w_sc, w_log_mag, w_lin_mag;        /* auraloss defaults 1, 1, 0 */
     int32_t sc_per_example;                  /* 1: mean over rows of per-row norm ratios (0.4.0); 0: global ratio */
     float eps;                               /* clamp of |X|^2, 1e-8 */
@@ -214,7 +214,8 @@ int mst_mrstft_init_tables(const mst_mrstft_desc* d, void* tables, void* stream)
 /* Per-call scratch; forward leaves what backward needs in it: the partial sums and coefficients, and - for the reference's
  * resolutions (512 / 2048 / 8192 points, hop = n_fft / 2) - the prediction's spectrum and the target's clamped magnitudes of every
  * bin and frame (12 bytes each; ~9.6 MB per row of 262144 samples): the backward reads them instead of transforming again, and
- * touches `pred` / `target` only on the generic path (other resolutions). */
+ * touches `pred` / `target` only on the generic path (other resolutions; rows that are not whole hops or shorter than two transforms;
+ * every 8192-point resolution after the first - and as soon as one resolution is generic, the whole backward is). */
 size_t mst_mrstft_workspace_bytes(const mst_mrstft_desc* d);
 /* loss: one fp32 on the device. */
 int mst_mrstft_forward(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables,

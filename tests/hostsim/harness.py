@@ -97,8 +97,8 @@ def mrstft(pred, target, resolutions, w_sc=1.0, w_log_mag=1.0, w_lin_mag=0.0, sc
     d = _mrstft_desc(x.shape[0], x.shape[1], resolutions, w_sc, w_log_mag, w_lin_mag, sc_per_example, 1e-8)
     tb, wb = L.mst_mrstft_tables_bytes(d), L.mst_mrstft_workspace_bytes(d)
     assert tb > 0 and wb > 0
-    tables = torch.zeros(tb // 4)
-    ws = torch.zeros(wb // 4)
+    tables = _nan(tb // 4)
+    ws = _workspace(wb, float("nan"))  # the product allocates with torch.empty: the kernels must not rely on a cleared workspace
     L.mst_mrstft_init_tables(d, tables, None)
     loss = torch.zeros(1)
     L.mst_mrstft_forward(d, x, y, tables, loss, ws, wb, None)
