@@ -30,13 +30,15 @@ struct AfArgs {
     double* stats;        // (2*bs, 8) reduced statistics per (signal set, b), see k_af_stats / k_af_finish
     float* statpart;      // (sets*bs, n_statblk, 8) partials of the above
     float* bandpart;      // (4*bs, kAfBinSlices, 24) partial band energies
-    float* losses;        // 5 weighted loss scalars out
+    float* losses;        // 5 weighted loss scalars out; (bs, 5) on the per-item route
     float* coef;          // backward coefficients
-    const float* grad_losses;  // (5) upstream dL/d(loss_k)
+    const float* grad_losses;  // upstream dL/d(loss_k): item b reads row b * gstride - (5) with gstride 0, (bs, 5) with gstride 5
     float* grad_pred;     // (bs, 2, n)
     float* yframes;       // (2*bs, n_frames, kAfFft) windowed adjoint frames of the prediction's mid / side signals
     float weights[5];
     int bs, sets, n_frames, n_groups, n_statblk;
+    int div;      // the batch divisor of the five mean-squared errors: bs, or 1 on the per-item route (each item a batch of one)
+    int gstride;  // see grad_losses
     int64_t n;
 };
 

@@ -161,8 +161,8 @@ __device__ void af_features(const AfArgs& a, int b, const float* g, double* part
         const double ratp = pk / fmax(rp, 1e-8), ratt = pkt / fmax(rt, 1e-8);
         const double cfp = 20.0 * log10(fmax(ratp, 1e-8)), cft = 20.0 * log10(fmax(ratt, 1e-8));
         part[1] += (cfp - cft) * (cfp - cft);
-        double d_rms = g0 * (double)a.weights[0] * 2.0 * (rp - rt) / (2.0 * a.bs);
-        const double d_cf = g1 * (double)a.weights[1] * 2.0 * (cfp - cft) / (2.0 * a.bs);
+        double d_rms = g0 * (double)a.weights[0] * 2.0 * (rp - rt) / (2.0 * a.div);
+        const double d_cf = g1 * (double)a.weights[1] * 2.0 * (cfp - cft) / (2.0 * a.div);
         double d_pk = 0.0;
         if (ratp >= 1e-8) {
             d_pk = d_cf * c20 / pk;
@@ -175,7 +175,7 @@ __device__ void af_features(const AfArgs& a, int b, const float* g, double* part
         const double Sp = st[0][2], Dp = st[0][3], St = st[1][2], Dt = st[1][3];
         const double wp = Dp / fmax(Sp, 1e-8), wt = Dt / fmax(St, 1e-8);
         part[2] += (wp - wt) * (wp - wt);
-        const double dw = g2 * (double)a.weights[2] * 2.0 * (wp - wt) / a.bs;
+        const double dw = g2 * (double)a.weights[2] * 2.0 * (wp - wt) / a.div;
         const double dD = dw / fmax(Sp, 1e-8), dS = (Sp >= 1e-8) ? -dw * Dp / (Sp * Sp) : 0.0;
         cLL += (2.0 / N) * (dD + dS); cLR += (2.0 / N) * (-dD + dS);
         cRL += (2.0 / N) * (-dD + dS); cRR += (2.0 / N) * (dD + dS);
@@ -185,7 +185,7 @@ __device__ void af_features(const AfArgs& a, int b, const float* g, double* part
         const double Tp = ERp + ELp, Tt = ERt + ELt;
         const double ip = (ERp - ELp) / fmax(Tp, 1e-8), it = (ERt - ELt) / fmax(Tt, 1e-8);
         part[3] += (ip - it) * (ip - it);
-        const double di = g3 * (double)a.weights[3] * 2.0 * (ip - it) / a.bs;
+        const double di = g3 * (double)a.weights[3] * 2.0 * (ip - it) / a.div;
         const double Tc = fmax(Tp, 1e-8);
         const double dT = (Tp >= 1e-8) ? -di * (ERp - ELp) / (Tc * Tc) : 0.0;
         cLL += (-di / Tc + dT) * 2.0 / N;
@@ -198,15 +198,17 @@ __device__ void af_features(const AfArgs& a, int b, const float* g, double* part
     }
 }
 
-// ---- final: the five weighted MSE losses.  One 64-lane workgroup.
-__global__ __launch_bounds__(64) void k_af_final(AfArgs a) {
+// ---- final: the five weighted MSE losses of items [b0, b0 + nb) over the divisor a.div, by one 64-lane workgroup.
+__device__ __forceinline__ void af_final(const AfArgs& a, int b0, int nb, float* losses) {
     __shared__ double acc[5];
     const int tid = threadIdx.x;
     double part[5] = {0, 0, 0, 0, 0};
-    for (int b = tid; b < a.bs; b += 64) af_features(a, b, nullptr, part, nullptr);
-    // bark MSE over (bs, 24, 2): signals 0..bs-1 pred mid, bs..2bs-1 pred side, then the target's
-    for (int i = tid; i < 2 * a.bs * kAfBands; i += 64) {
-        const double d = (double)a.bark[i] - (double)a.bark[2 * a.bs * kAfBands + i];
+    for (int b = tid; b < nb; b += 64) af_features(a, b0 + b, nullptr, part, nullptr);
+    // bark MSE over (nb, 24, 2): signals 0..bs-1 pred mid, bs..2bs-1 pred side, then the target's
+    for (int i = tid; i < 2 * nb * kAfBands; i += 64) {
+        const int which = i / (nb * kAfBands), rem = i % (nb * kAfBands);
+        const int at = (which * a.bs + b0) * kAfBands + rem;  // = i for the whole batch
+        const double d = (double)a.bark[at] - (double)a.bark[2 * a.bs * kAfBands + at];
         part[4] += d * d;
     }
     for (int q = 0; q < 5; ++q) {
@@ -216,16 +218,19 @@ __global__ __launch_bounds__(64) void k_af_final(AfArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-        a.losses[0] = (float)(a.weights[0] * acc[0] / (2.0 * a.bs));
-        a.losses[1] = (float)(a.weights[1] * acc[1] / (2.0 * a.bs));
-        a.losses[2] = (float)(a.weights[2] * acc[2] / a.bs);
-        a.losses[3] = (float)(a.weights[3] * acc[3] / a.bs);
-        a.losses[4] = (float)(a.weights[4] * acc[4] / (2.0 * a.bs * kAfBands));
+        losses[0] = (float)(a.weights[0] * acc[0] / (2.0 * a.div));
+        losses[1] = (float)(a.weights[1] * acc[1] / (2.0 * a.div));
+        losses[2] = (float)(a.weights[2] * acc[2] / a.div);
+        losses[3] = (float)(a.weights[3] * acc[3] / a.div);
+        losses[4] = (float)(a.weights[4] * acc[4] / (2.0 * a.div * kAfBands));
     }
 }
+__global__ __launch_bounds__(64) void k_af_final(AfArgs a) { af_final(a, 0, a.bs, a.losses); }
+// one item per workgroup, each a batch of one (a.div = 1): row b of (bs, 5).  grid (bs)
+__global__ __launch_bounds__(64) void k_af_final_items(AfArgs a) { af_final(a, blockIdx.x, 1, a.losses + 5 * blockIdx.x); }
 __global__ __launch_bounds__(64) void k_af_coef(AfArgs a) {
     double part[4] = {0, 0, 0, 0};
-    for (int b = threadIdx.x; b < a.bs; b += 64) af_features(a, b, a.grad_losses, part, a.coef + (int64_t)b * 16);
+    for (int b = threadIdx.x; b < a.bs; b += 64) af_features(a, b, a.grad_losses + (int64_t)b * a.gstride, part, a.coef + (int64_t)b * 16);
 }
 
 // ---- feature profile (include/diffmst_hip.h: MST_AF_PROFILE_DOUBLES) ----------------------------------
@@ -255,14 +260,15 @@ __global__ __launch_bounds__(64) void k_af_profile_unpack(AfArgs a, const double
 }
 
 // ---- backward ---------------------------------------------------------------------------------------
-// dM[s][k] = sum_j (w4 * 2 (B - Bt) / (2 bs 24)) / (lin_j + 1e-8) * fb[k][j] / F   for the 2*bs prediction signals
+// dM[s][k] = sum_j (g4[b] w4 * 2 (B - Bt) / (2 div 24)) / (lin_j + 1e-8) * fb[k][j] / F   for the 2*bs prediction signals
 __global__ __launch_bounds__(256) void k_af_bark_dmag(AfArgs a) {
     __shared__ float cj[kAfBands];
     const int tid = threadIdx.x, s = blockIdx.y;  // s < 2*bs
     if (tid < kAfBands) {
         const float B = a.bark[(int64_t)s * kAfBands + tid], Bt = a.bark[(int64_t)(2 * a.bs + s) * kAfBands + tid];
         const float lin = a.bark[(int64_t)(4 * a.bs + s) * kAfBands + tid];
-        cj[tid] = a.grad_losses[4] * a.weights[4] * 2.0f * (B - Bt) / (2.0f * a.bs * kAfBands) / (lin + 1e-8f) / (float)a.n_frames;
+        const float g4 = a.grad_losses[(s % a.bs) * a.gstride + 4];  // the item's own cotangent on the per-item route
+        cj[tid] = g4 * a.weights[4] * 2.0f * (B - Bt) / (2.0f * a.div * kAfBands) / (lin + 1e-8f) / (float)a.n_frames;
     }
     __syncthreads();
     const int k = blockIdx.x * 256 + tid;
@@ -423,7 +429,7 @@ static AfArgs af_args(const AfPlan& p, int bs, int64_t n, const float* pred, con
     a.yframes = ws + p.yframes;
     a.bandpart = ws + p.bandpart; a.stats = reinterpret_cast<double*>(ws + p.stats);
     for (int i = 0; i < 5; ++i) a.weights[i] = weights[i];
-    a.bs = bs; a.sets = target ? 2 : 1; a.n_frames = p.n_frames; a.n_groups = p.n_groups; a.n_statblk = p.n_statblk; a.n = n;
+    a.bs = bs; a.div = bs; a.gstride = 0; a.sets = target ? 2 : 1; a.n_frames = p.n_frames; a.n_groups = p.n_groups; a.n_statblk = p.n_statblk; a.n = n;
     return a;
 }
 // statistics and band energies of a.sets signal sets into `stats` and `bark`
@@ -531,5 +537,39 @@ extern "C" int mst_afloss_backward_profile(const float* pred, const double* prof
     a.grad_losses = grad_losses5;
     a.grad_pred = grad_pred;
     af_backward(a, stream);  // reads what mst_afloss_forward_profile left in the workspace, the unpacked profile included
+    return (int)hipGetLastError();
+}
+
+// ---- per-item loss against a profile: every item a batch of one, a cotangent row per item -----------------------------------------
+extern "C" int mst_afloss_forward_profile_items(const float* pred, const double* profile, int32_t bs, int64_t n_samples,
+                                                const float* weights5, const void* tables, const float* filterbank, float* losses,
+                                                void* workspace, size_t workspace_bytes, void* stream_) {
+    const AfPlan p = af_plan(bs, n_samples, 1);
+    if (!p.ok || !pred || !profile || !weights5 || !tables || !filterbank || !losses || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    AfArgs a = af_args(p, bs, n_samples, pred, nullptr, (const float*)tables, filterbank, weights5, (float*)workspace);
+    a.losses = losses;
+    a.div = 1;
+    af_analyse(a, stream);
+    hipLaunchKernelGGL(k_af_profile_unpack, dim3(bs), dim3(64), 0, stream, a, profile);
+    hipLaunchKernelGGL(k_af_final_items, dim3(bs), dim3(64), 0, stream, a);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_afloss_backward_profile_items(const float* pred, const double* profile, int32_t bs, int64_t n_samples,
+                                                 const float* weights5, const void* tables, const float* filterbank,
+                                                 const float* grad_losses, float* grad_pred, void* workspace, size_t workspace_bytes,
+                                                 void* stream_) {
+    const AfPlan p = af_plan(bs, n_samples, 1);
+    if (!p.ok || !pred || !profile || !weights5 || !tables || !filterbank || !grad_losses || !grad_pred || !workspace)
+        return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    AfArgs a = af_args(p, bs, n_samples, pred, nullptr, (const float*)tables, filterbank, weights5, (float*)workspace);
+    a.grad_losses = grad_losses;
+    a.gstride = 5;
+    a.div = 1;
+    a.grad_pred = grad_pred;
+    af_backward(a, stream);  // reads what mst_afloss_forward_profile_items left in the workspace
     return (int)hipGetLastError();
 }

@@ -21,7 +21,8 @@ namespace mst {
 
 constexpr int kOptWG = 256;
 constexpr int kOptHdr = 16;               // int32 words in front of the moments (include/diffmst_hip.h)
-constexpr int64_t kOptMaxParams = 1 << 20;
+constexpr int64_t kOptMaxParams = 1 << 20;  // per item
+constexpr int kOptMaxItems = 1024;
 
 struct OptArgs {
     float* theta[MST_OPT_MAX_SEGMENTS];
@@ -37,22 +38,33 @@ struct OptArgs {
 __device__ __forceinline__ bool opt_finite(float x) { return (__float_as_int(x) & 0x7f800000) != 0x7f800000; }
 __device__ __forceinline__ float opt_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// state words [0, 16 + 2 n) <- 0, p <- sigmoid(theta)
-__global__ __launch_bounds__(kOptWG) void k_logit_adam_init(OptArgs a, int32_t* __restrict__ state) {
+// One workgroup's share of the init: state words [0, 16 + 2 n) <- 0, p <- sigmoid(theta).  `item` selects the slice
+// [item count, (item + 1) count) of every segment (count = a.count[s], the per-item count) and `state` is that item's block; the
+// single-song kernel is item 0 of one.
+__device__ __forceinline__ void opt_init(const OptArgs& a, int item, int32_t* __restrict__ state) {
     const int tid = threadIdx.x;
     const int words = kOptHdr + 2 * a.n_params;
     for (int w = tid; w < words; w += kOptWG) state[w] = 0;
 #pragma unroll
     for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
         if (s >= a.n_segments) break;
-        const float* __restrict__ th = a.theta[s];
-        float* __restrict__ p = a.p[s];
+        const int64_t off = (int64_t)item * a.count[s];
+        const float* __restrict__ th = a.theta[s] + off;
+        float* __restrict__ p = a.p[s] + off;
         for (int i = tid; i < a.count[s]; i += kOptWG) p[i] = opt_sigmoid(th[i]);
     }
 }
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_init(OptArgs a, int32_t* __restrict__ state) { opt_init(a, 0, state); }
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_init_batch(OptArgs a, int32_t* __restrict__ state) {
+    const int item = blockIdx.x;
+    opt_init(a, item, state + (int64_t)item * (kOptHdr + 2 * a.n_params));
+}
 
-__global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __restrict__ row, double lr, double beta1, double beta2,
-                                                            float eps, int32_t* __restrict__ state) {
+// One workgroup's whole step over its item's slices: the body of both kernels below.  term(k) is loss term k of this item, `row` its
+// history row, `state` its block (header, first moments, second moments).
+template <class Term>
+__device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, float* __restrict__ row, double lr, double beta1,
+                                         double beta2, float eps, int32_t* __restrict__ state) {
     __shared__ int s_bad;
     __shared__ float s_step, s_c2;
     const int tid = threadIdx.x;
@@ -62,11 +74,11 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __
 #pragma unroll
     for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
         if (s >= a.n_segments) break;
-        const float* __restrict__ dp = a.grad_p[s];
-        if (!dp) continue;
+        if (!a.grad_p[s]) continue;
+        const float* __restrict__ dp = a.grad_p[s] + (int64_t)item * a.count[s];
         for (int i = tid; i < a.count[s]; i += kOptWG) bad |= !opt_finite(dp[i]);
     }
-    if (tid < a.n_terms) bad |= !opt_finite(*a.term[tid]);
+    if (tid < a.n_terms) bad |= !opt_finite(term(tid));
     if (bad) atomicMax(&s_bad, 1);
     if (tid == 0) {  // the two bias corrections of step t = state[0] + 1, in float64, rounded once
         const double t = (double)(state[0] + 1);
@@ -78,9 +90,9 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __
     if (tid == 0) {
         float sum = 0.0f;  // the script's `loss = 0; loss += value`, left to right
         for (int k = 0; k < a.n_terms; ++k) {
-            const float term = *a.term[k];
-            sum += term;
-            row[1 + k] = term;
+            const float value = term(k);
+            sum += value;
+            row[1 + k] = value;
         }
         row[0] = sum;
         const int32_t iteration = state[3];
@@ -100,10 +112,11 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __
     for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
         if (s >= a.n_segments) break;
         const int n = a.count[s];
-        const float* __restrict__ dp = a.grad_p[s];
-        if (dp) {  // a NULL gradient is a parameter without .grad: torch skips it, its logits, moments and p keep their bits
-            float* __restrict__ th = a.theta[s];
-            float* __restrict__ p = a.p[s];
+        if (a.grad_p[s]) {  // a NULL gradient is a parameter without .grad: torch skips it, its logits, moments and p keep their bits
+            const int64_t off = (int64_t)item * n;
+            const float* __restrict__ dp = a.grad_p[s] + off;
+            float* __restrict__ th = a.theta[s] + off;
+            float* __restrict__ p = a.p[s] + off;
             float* __restrict__ m = m_all + at;
             float* __restrict__ v = v_all + at;
             for (int i = tid; i < n; i += kOptWG) {
@@ -122,22 +135,38 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __
     }
 }
 
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __restrict__ row, double lr, double beta1, double beta2,
+                                                            float eps, int32_t* __restrict__ state) {
+    opt_step(a, 0, [&](int k) { return *a.term[k]; }, row, lr, beta1, beta2, eps, state);
+}
+// Batched fits (include/diffmst_hip.h): workgroup b is the single kernel on item b - its slice of every segment, row b of the dense
+// (items, n_terms) loss terms, history row b, state block b, its own "not finite" flag in its own LDS.  Workgroups exchange nothing.
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_batch(OptArgs a, const float* __restrict__ terms, float* __restrict__ rows,
+                                                                  double lr, double beta1, double beta2, float eps,
+                                                                  int32_t* __restrict__ state) {
+    const int item = blockIdx.x;
+    const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
+    opt_step(a, item, [&](int k) { return mine[k]; }, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+             state + (int64_t)item * (kOptHdr + 2 * a.n_params));
+}
+
 namespace {
 // the segment table as kernel arguments; false for what the kernels do not support
-bool opt_args(const mst_logit_adam_segment* segments, int32_t n_segments, OptArgs& a) {
-    if (!segments || n_segments < 1 || n_segments > MST_OPT_MAX_SEGMENTS) return false;
+// (a.count and a.n_params are per item: every count must divide by `items`, 1 for the single-song calls)
+bool opt_args(const mst_logit_adam_segment* segments, int32_t n_segments, OptArgs& a, int32_t items = 1) {
+    if (!segments || n_segments < 1 || n_segments > MST_OPT_MAX_SEGMENTS || items < 1 || items > kOptMaxItems) return false;
     a = OptArgs{};
     int64_t total = 0;
     for (int s = 0; s < n_segments; ++s) {
         const mst_logit_adam_segment& g = segments[s];
-        if (!g.theta || !g.p || g.count < 1 || g.count > kOptMaxParams || ((uintptr_t)g.theta & 3) || ((uintptr_t)g.p & 3) ||
-            ((uintptr_t)g.grad_p & 3))
+        if (!g.theta || !g.p || g.count < 1 || g.count % items || g.count / items > kOptMaxParams || ((uintptr_t)g.theta & 3) ||
+            ((uintptr_t)g.p & 3) || ((uintptr_t)g.grad_p & 3))
             return false;
         a.theta[s] = g.theta;
         a.p[s] = g.p;
         a.grad_p[s] = g.grad_p;
-        a.count[s] = (int32_t)g.count;
-        total += g.count;
+        a.count[s] = (int32_t)(g.count / items);
+        total += g.count / items;
     }
     if (total > kOptMaxParams) return false;
     a.n_segments = n_segments;
@@ -174,5 +203,34 @@ extern "C" int mst_logit_adam_step(const mst_logit_adam_segment* segments, int32
     a.n_terms = n_terms;
     hipLaunchKernelGGL(k_logit_adam_step, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, history_row, lr, beta1, beta2, (float)eps,
                        (int32_t*)state);
+    return (int)hipGetLastError();
+}
+
+// ---- batched fits: `items` independent optimisations in one launch, one workgroup each ---------------------------------------------
+static bool opt_hyper_ok(double lr, double beta1, double beta2, double eps) {
+    return lr > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0;
+}
+extern "C" size_t mst_logit_adam_batch_state_bytes(int32_t items, int64_t params_per_item) {
+    if (items < 1 || items > kOptMaxItems || params_per_item < 1 || params_per_item > kOptMaxParams) return 0;
+    return (size_t)items * ((size_t)kOptHdr + 2 * (size_t)params_per_item) * 4;
+}
+extern "C" int mst_logit_adam_init_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, void* state,
+                                         void* stream) {
+    OptArgs a;
+    if (!opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_logit_adam_init_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, (int32_t*)state);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_logit_adam_step_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items,
+                                         const float* loss_terms, int32_t n_terms, float* history_rows, double lr, double beta1,
+                                         double beta2, double eps, void* state, void* stream) {
+    OptArgs a;
+    if (!opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3) || !history_rows ||
+        ((uintptr_t)history_rows & 3) || !loss_terms || ((uintptr_t)loss_terms & 3) || n_terms < 1 || n_terms > MST_OPT_MAX_TERMS)
+        return hipErrorInvalidValue;
+    if (!opt_hyper_ok(lr, beta1, beta2, eps)) return hipErrorInvalidValue;
+    a.n_terms = n_terms;
+    hipLaunchKernelGGL(k_logit_adam_step_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms, history_rows, lr,
+                       beta1, beta2, (float)eps, (int32_t*)state);
     return (int)hipGetLastError();
 }

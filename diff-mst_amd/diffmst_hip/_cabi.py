@@ -119,6 +119,8 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
 
 
 OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
+OPT_MAX_ITEMS = 1024  # items of mst_logit_adam_step_batch
+OPT_HEADER_WORDS = 16  # int32 words in front of an item's moments
 AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
 
 
@@ -206,6 +208,10 @@ SIGNATURES = {
     "mst_logit_adam_init": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, _P, _S]),
     "mst_logit_adam_step": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _P, C.c_double, C.c_double,
                                      C.c_double, C.c_double, _P, _S]),
+    "mst_logit_adam_batch_state_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "mst_logit_adam_init_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, _S]),
+    "mst_logit_adam_step_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_double,
+                                           C.c_double, C.c_double, _P, _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
@@ -225,6 +231,9 @@ SIGNATURES = {
     "mst_afloss_profile_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "mst_afloss_forward_profile": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_afloss_backward_profile": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_afloss_forward_profile_items": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_afloss_backward_profile_items": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t,
+                                                   _S]),
     "mst_ctrl_workspace_bytes": (C.c_size_t, [C.POINTER(CtrlDesc)]),
     "mst_ctrl_forward": (STATUS, [C.POINTER(CtrlDesc), _P, _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),
     "mst_ctrl_backward": (STATUS, [C.POINTER(CtrlDesc), _P, C.POINTER(CtrlLayer), _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),

@@ -315,6 +315,42 @@ class _AudioFeatureProfileFunction(torch.autograd.Function):
         return gx.view(shape), None, None, None
 
 
+class _AudioFeatureItemsFunction(torch.autograd.Function):
+    """``_AudioFeatureProfileFunction`` with every batch item a loss of its own: five ``(bs,)`` outputs, a cotangent per item."""
+
+    @staticmethod
+    def forward(ctx, pred, profile, weights, sample_rate):
+        lib = _hip.lib()
+        x = pred.float().contiguous()
+        bs, _, n = x.shape
+        dev = x.device
+        tables, fb = _af_constants(dev, sample_rate)
+        nbytes = lib.mst_afloss_profile_workspace_bytes(bs, n)
+        if nbytes == 0:
+            raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        losses = torch.empty(bs, 5, dtype=torch.float32, device=dev)
+        w = (ctypes.c_float * 5)(*[float(v) for v in weights])
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_forward_profile_items(x, profile, bs, n, w, tables, fb, losses, ws, nbytes, st)
+        ctx.meta = (bs, n, w, nbytes, pred.shape)
+        ctx.save_for_backward(x, profile, tables, fb, ws)
+        return tuple(losses.unbind(1))  # five (bs,) views of one buffer
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_each):
+        x, profile, tables, fb, ws = ctx.saved_tensors
+        bs, n, w, nbytes, shape = ctx.meta
+        lib = _hip.lib()
+        dev = x.device
+        g = torch.stack([gi.float().reshape(bs) for gi in grad_each], dim=1).contiguous()  # (bs, 5)
+        gx = torch.empty_like(x)
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_backward_profile_items(x, profile, bs, n, w, tables, fb, g, gx, ws, nbytes, st)
+        return gx.view(shape), None, None, None
+
+
 class AudioFeatureLoss(torch.nn.Module):
     """Drop-in for reference ``mst.loss.AudioFeatureLoss`` (:198-260).
 
@@ -360,6 +396,35 @@ class AudioFeatureLoss(torch.nn.Module):
         with _hip.launch_on(dev) as st:
             lib.mst_af_profile(x, bs, n, tables, fb, data, ws, nbytes, st)
         return AudioFeatureProfile(data, self.sample_rate, n)
+
+    def per_item(self, input: torch.Tensor, target):
+        """The five terms of every batch item on its own: ``{key: (bs,) float32 device tensor}``, row ``b`` what ``forward`` returns for
+        ``input[b:b + 1]`` alone (the batch mean of each key is ``forward``'s value), differentiable in ``input``; a cotangent on
+        element ``b`` reaches ``input[b]`` only.  For a batch of independent fits (``mst.online.optimize_batch``): under ``forward``
+        every item's gradient carries the factor ``1 / bs``, which Adam's ``eps`` makes visible.
+
+        ``target`` is an ``AudioFeatureProfile`` of batch size ``bs`` or 1 (one reference for every item) or a ``(bs, 2, m)`` tensor of
+        any length ``m > 16384``, which is profiled on the way - also when ``m == seq_len``: this route has no paired kernels."""
+        is_profile = isinstance(target, AudioFeatureProfile)
+        if not is_profile and not isinstance(target, torch.Tensor):
+            raise TypeError(f"AudioFeatureLoss takes a tensor or an AudioFeatureProfile as target, got {type(target).__name__}")
+        _hip.require_cuda(input, target.data if is_profile else target)
+        _af_check_input(input, "input")
+        bs = input.shape[0]
+        if is_profile:
+            if target.sample_rate != self.sample_rate:
+                raise ValueError(f"the profile was taken at {target.sample_rate} Hz, this loss runs at {self.sample_rate} Hz")
+        else:
+            _af_check_input(target, "target")
+        have = target.batch_size if is_profile else target.shape[0]
+        if have != bs and not (is_profile and have == 1):
+            raise ValueError(f"input has batch size {bs}, the target {have}")
+        if not is_profile:
+            target = self.profile(target)
+        _hip.require_same_device(input.device, target.data)
+        data = target.data if have == bs else target.data.expand(bs, -1).contiguous()
+        losses = _AudioFeatureItemsFunction.apply(input, data, tuple(self.weights), self.sample_rate)
+        return dict(zip(AF_KEYS, losses))
 
     def forward(self, input: torch.Tensor, target):
         if isinstance(target, torch.Tensor) and target.shape == input.shape:

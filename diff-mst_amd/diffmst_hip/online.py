@@ -1,4 +1,5 @@
-"""Per-song mix optimisation on the device: ``optimize()`` and the block renderer of the reference's ``scripts/online.py``.
+"""Per-song mix optimisation on the device: ``optimize()`` and the block renderer of the reference's ``scripts/online.py``, and
+``optimize_batch()`` / ``pick()``: many such fits in the launches of one.
 
 ``optimize`` fits the console's parameters to a reference mix by gradient descent on their logits - no model involved (reference
 scripts/online.py:15-123).  The console, the loss and their backwards are the package's kernels; everything the script does around them
@@ -38,35 +39,86 @@ def _segments(logits, params, grads):
     return seg
 
 
-def _init(logits, params):
-    """p <- sigmoid(logits) by the kernel every later p comes from, and a zeroed optimiser state."""
+def _init(logits, params, items=None):
+    """p <- sigmoid(logits) by the kernel every later p comes from, and a zeroed optimiser state: one block, or with ``items`` one
+    block per item of the leading dimension."""
     lib = _hip.lib()
     dev = logits[0].device
-    nbytes = lib.mst_logit_adam_state_bytes(sum(t.numel() for t in logits))
+    total = sum(t.numel() for t in logits)
+    none = (None,) * len(logits)
+    if items is None:
+        nbytes = lib.mst_logit_adam_state_bytes(total)
+    else:
+        nbytes = lib.mst_logit_adam_batch_state_bytes(items, total // items)
     if nbytes == 0:
-        raise ValueError("more parameters than the logit-Adam kernel takes (2^20)")
+        raise ValueError(f"more parameters per fit than the logit-Adam kernel takes (2^20), or more than {_cabi.OPT_MAX_ITEMS} fits")
     state = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     with _hip.launch_on(dev) as st:
-        lib.mst_logit_adam_init(_segments(logits, params, (None,) * len(logits)), len(logits), state, st)
+        if items is None:
+            lib.mst_logit_adam_init(_segments(logits, params, none), len(logits), state, st)
+        else:
+            lib.mst_logit_adam_init_batch(_segments(logits, params, none), len(logits), items, state, st)
     return state
 
 
-class _Run:
-    """One optimisation: set-up (the start point goes to the device), ``iterate(n)`` (nothing in it waits for the device) and
-    ``finish()`` (the one read of history and status)."""
+def _check_single(tracks, ref_mix, is_profile):
+    _hip.require_cuda(tracks, ref_mix.data if is_profile else ref_mix)
+    if tracks.dim() != 2:
+        raise ValueError(f"tracks must be (n_tracks, n_samples), got {tuple(tracks.shape)} (one song per call: no batch dimension)")
+    if is_profile:
+        if ref_mix.batch_size != 1:
+            raise ValueError(f"a profile given as ref_mix must have batch size 1, got {ref_mix.batch_size}")
+    elif ref_mix.dim() != 2 or ref_mix.shape[0] != 2:
+        raise ValueError(f"ref_mix must be (2, n_samples) or an AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+    return None
 
-    def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags):
+
+def _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch):
+    """Types and shapes of ``optimize_batch``, before anything touches the device -> (B, init scales)."""
+    if not callable(getattr(loss_function, "per_item", None)):
+        raise TypeError("optimize_batch needs a loss_function with a per_item(input, target) method (AudioFeatureLoss.per_item): "
+                        f"{type(loss_function).__name__} has none")
+    if not isinstance(tracks, torch.Tensor) or tracks.dim() not in (2, 3):
+        raise ValueError("tracks must be (B, n_tracks, n_samples), or (n_tracks, n_samples) with batch=B")
+    if tracks.dim() == 3:
+        if batch is not None and int(batch) != tracks.shape[0]:
+            raise ValueError(f"batch={batch} with tracks of batch size {tracks.shape[0]}")
+        B = tracks.shape[0]
+    elif batch is None:
+        raise ValueError("tracks of shape (n_tracks, n_samples) need batch=B (the song is repeated B times)")
+    else:
+        B = int(batch)
+    if not 1 <= B <= _cabi.OPT_MAX_ITEMS:
+        raise ValueError(f"the batch size must be 1..{_cabi.OPT_MAX_ITEMS}, got {B}")
+    if is_profile:
+        if ref_mix.batch_size not in (1, B):
+            raise ValueError(f"a profile given as ref_mix must have batch size {B} or 1, got {ref_mix.batch_size}")
+    elif not (ref_mix.dim() == 2 and ref_mix.shape[0] == 2) and not (ref_mix.dim() == 3 and tuple(ref_mix.shape[:2]) == (B, 2)):
+        raise ValueError(f"ref_mix must be ({B}, 2, n_samples), (2, n_samples) or an AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+    if isinstance(init_scale, (int, float)):
+        scales = [float(init_scale)] * B
+    else:
+        scales = [float(v) for v in init_scale]
+        if len(scales) != B:
+            raise ValueError(f"init_scale must be a number or a sequence of {B} numbers, got {len(scales)}")
+    _hip.require_cuda(tracks, ref_mix.data if is_profile else ref_mix)
+    return B, scales
+
+
+class _Run:
+    """One optimisation, or with ``batch`` a batch of independent ones in the same launches: set-up (the start point goes to the
+    device), ``iterate(n)`` (nothing in it waits for the device) and ``finish()`` (the one read of history and status)."""
+
+    def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
+                 batch=None, batched=False):
         is_profile = isinstance(ref_mix, AudioFeatureProfile)
         if not is_profile and not isinstance(ref_mix, torch.Tensor):
             raise TypeError(f"ref_mix must be a (2, n_samples) tensor or an AudioFeatureProfile, got {type(ref_mix).__name__}")
-        _hip.require_cuda(tracks, ref_mix.data if is_profile else ref_mix)
-        if tracks.dim() != 2:
-            raise ValueError(f"tracks must be (n_tracks, n_samples), got {tuple(tracks.shape)} (one song per call: no batch dimension)")
-        if is_profile:
-            if ref_mix.batch_size != 1:
-                raise ValueError(f"a profile given as ref_mix must have batch size 1, got {ref_mix.batch_size}")
-        elif ref_mix.dim() != 2 or ref_mix.shape[0] != 2:
-            raise ValueError(f"ref_mix must be (2, n_samples) or an AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+        if batched:
+            self.items, scales = _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch)
+        else:
+            self.items = _check_single(tracks, ref_mix, is_profile)
+        B = self.items
         _hip.require_same_device(tracks.device, ref_mix.data if is_profile else ref_mix)
         if int(n_iters) < 1:
             raise ValueError("n_iters must be at least 1")
@@ -74,61 +126,93 @@ class _Run:
         self.console, self.loss_function, self.callback = mix_console, loss_function, callback
         self.flags = dict(use_fx_bus=False)
         self.flags.update(console_flags)
-        self.tracks = tracks.detach().unsqueeze(0)
+        n_tracks, n_samples = tracks.shape[-2:]
+        if B is None:
+            self.tracks = tracks.detach().unsqueeze(0)
+        else:
+            self.tracks = tracks.detach() if tracks.dim() == 3 else tracks.detach().unsqueeze(0).repeat(B, 1, 1)
         if is_profile:
             self.ref_mix = ref_mix
         else:
-            self.ref_mix = ref_mix.detach().unsqueeze(0)
-            if ref_mix.shape[1] != tracks.shape[1] and hasattr(loss_function, "profile"):
-                # a reference of another length (the usual case: it is another song) is analysed here, once; the loop gets the profile
+            self.ref_mix = ref_mix.detach()
+            if self.ref_mix.dim() == 2:
+                self.ref_mix = self.ref_mix.unsqueeze(0)
+            if (B is not None or ref_mix.shape[-1] != n_samples) and hasattr(loss_function, "profile"):
+                # a reference of another length (the usual case: it is another song) is analysed here, once; the loop gets the profile.
+                # A batch always takes the profile: its loss has no paired route
                 self.ref_mix = loss_function.profile(self.ref_mix)
+            elif B is not None and self.ref_mix.shape[0] != B:
+                self.ref_mix = self.ref_mix.expand(B, -1, -1)
         self.n_iters = int(n_iters)
         self.hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps))
-        start = start_point(tracks.shape[0], mix_console, init_scale, generator)
-        # the shapes the console takes: (1, T, 27), (1, 25), (1, 26)
-        self.logits = tuple(t.to(device=dev, dtype=torch.float32).reshape((1,) + (t.shape if i == 0 else t.shape[1:])).contiguous()
-                            for i, t in enumerate(start))
+        if B is None:
+            start = start_point(n_tracks, mix_console, init_scale, generator)
+            # the shapes the console takes: (1, T, 27), (1, 25), (1, 26)
+            self.logits = tuple(t.to(device=dev, dtype=torch.float32).reshape((1,) + (t.shape if i == 0 else t.shape[1:])).contiguous()
+                                for i, t in enumerate(start))
+        else:
+            # item b starts at the b-th successive draw, so B = 1 starts where optimize() does: (B, T, 27), (B, 25), (B, 26)
+            draws = [start_point(n_tracks, mix_console, scale, generator) for scale in scales]
+            self.logits = tuple(torch.stack([d[i] if i == 0 else d[i][0] for d in draws]).to(device=dev, dtype=torch.float32).contiguous()
+                                for i in range(3))
         self.params = tuple(torch.empty_like(t).requires_grad_(True) for t in self.logits)  # leaves the kernel rewrites
-        self.state = _init(self.logits, self.params)
+        self.state = _init(self.logits, self.params, B)
         self.one = torch.ones((), dtype=torch.float32, device=dev)
         self.keys, self.history, self.result = None, None, None
 
     def iterate(self, n):
         lib = _hip.lib()
+        B = self.items
         self.result = result = self.console(self.tracks, *self.params, **self.flags)
-        losses = self.loss_function(result[1], self.ref_mix)
+        losses = (self.loss_function if B is None else self.loss_function.per_item)(result[1], self.ref_mix)
         keys, terms = (tuple(losses), list(losses.values())) if isinstance(losses, dict) else ((), [losses])
         if self.keys is None:
             if not 1 <= len(terms) <= _cabi.OPT_MAX_TERMS:
                 raise ValueError(f"the loss must return 1..{_cabi.OPT_MAX_TERMS} terms, got {len(terms)}")
             self.keys = keys
-            self.history = torch.empty(self.n_iters, 1 + len(terms), dtype=torch.float32, device=self.tracks.device)
+            shape = (self.n_iters, 1 + len(terms)) if B is None else (self.n_iters, B, 1 + len(terms))
+            self.history = torch.empty(shape, dtype=torch.float32, device=self.tracks.device)
         elif keys != self.keys:
             raise ValueError(f"the loss returned {keys} after {self.keys}: its terms must not change between iterations")
         for t in terms:
-            if not isinstance(t, torch.Tensor) or t.numel() != 1 or t.dtype != torch.float32 or not t.is_cuda:
-                raise TypeError("every loss term must be a one-element float32 device tensor")
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or (
+                    t.numel() != 1 if B is None else tuple(t.shape) != (B,)):
+                raise TypeError("every loss term must be a one-element float32 device tensor" if B is None else
+                                f"every per-item loss term must be a ({B},) float32 device tensor")
         grads = torch.autograd.grad(terms, self.params, [self.one.expand(t.shape) for t in terms], allow_unused=True)
         grads = tuple(None if g is None else g.float().contiguous() for g in grads)
         if self.callback is not None:
             self.callback(n, SimpleNamespace(params=self.params, grads=grads, losses=dict(zip(keys, terms)) if keys else terms[0],
                                              logits=self.logits))
-        term_ptrs = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
-        row = self.history.data_ptr() + 4 * n * self.history.shape[1]
-        with _hip.launch_on(self.tracks.device) as st:
-            lib.mst_logit_adam_step(_segments(self.logits, self.params, grads), len(self.logits), term_ptrs, len(terms), row,
-                                    *self.hyper, self.state, st)
+        row = self.history.data_ptr() + 4 * n * self.history[0].numel()
+        segments = _segments(self.logits, self.params, grads)
+        if B is None:
+            term_ptrs = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
+            with _hip.launch_on(self.tracks.device) as st:
+                lib.mst_logit_adam_step(segments, len(self.logits), term_ptrs, len(terms), row, *self.hyper, self.state, st)
+        else:
+            dense = torch.stack([t.detach() for t in terms], dim=1)  # (B, n_terms), after the callback: it sees what the callback left
+            with _hip.launch_on(self.tracks.device) as st:
+                lib.mst_logit_adam_step_batch(segments, len(self.logits), B, dense, len(terms), row, *self.hyper, self.state, st)
 
     def finish(self):
         history = self.history.cpu()  # the one wait of the run
+        names = ("loss",) + self.keys
+        _, mix, track_dict, fx_dict, master_dict = self.result
+        lt, lf, lm = self.logits
+        if self.items is not None:
+            words = self.state.view(self.items, -1)[:, :4].tolist()
+            stopped_at = [where if status else None for _, status, where, _ in words]
+            if all(w is not None for w in stopped_at):
+                raise FloatingPointError(f"optimize_batch: every item met a loss term or a gradient that was not finite (first at "
+                                         f"iterations {stopped_at}); those iterations left the parameters as they stood")
+            loss_history = {name: history[:, :, i].clone() for i, name in enumerate(names)}
+            return mix.detach(), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at
         t, status, where, _ = self.state[:4].tolist()
         if status:
             raise FloatingPointError(f"optimize: a loss term or a gradient was not finite at iteration {where}; the parameters were "
                                      f"left as they stood ({t} updates applied)")
-        names = ("loss",) + self.keys
         loss_history = {name: history[:, i].tolist() for i, name in enumerate(names)}
-        _, mix, track_dict, fx_dict, master_dict = self.result
-        lt, lf, lm = self.logits
         return mix.detach().squeeze(0), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history
 
 
@@ -173,6 +257,47 @@ def optimize(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1
     for n in range(run.n_iters):
         run.iterate(n)
     return run.finish()
+
+
+def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, batch=None, betas=(0.9, 0.999),
+                   eps=1e-8, generator=None, callback=None, **console_flags):
+    """``B`` independent ``optimize`` runs in the launches of one: random restarts, one song against several references, several songs
+    against one reference.  One console forward at batch ``B``, ``loss_function.per_item``, one ``torch.autograd.grad`` with a ones
+    cotangent per ``(B,)`` term and one ``mst_logit_adam_step_batch`` per iteration; nothing in the loop waits for the host.
+
+    ``tracks`` is ``(B, T, N)``, or ``(T, N)`` with ``batch=B`` (the song is repeated).  ``ref_mix`` is ``(B, 2, M)``, ``(2, M)`` (one
+    reference for every item) or an ``AudioFeatureProfile`` of batch size ``B`` or 1; a tensor is profiled once, before the loop.
+    ``loss_function`` must offer ``per_item(input, target)`` -> ``(B,)`` terms (``AudioFeatureLoss.per_item``): with a batch-mean loss
+    every item's gradient would carry ``1 / B``, which Adam's ``eps`` makes visible.  ``init_scale`` is a number or ``B`` numbers.  Item
+    ``b`` starts at the ``b``-th successive ``start_point()`` draw from the generator, so ``B = 1`` starts where ``optimize`` starts.
+
+    Returns ``optimize``'s 8-tuple with a leading batch dimension everywhere, plus ``stopped_at``: ``mix (B, 2, N)``, logits
+    ``(B, T, 27)``, ``(B, 25)``, ``(B, 26)``, the console's dictionaries at batch ``B``, ``loss_history[name]`` an ``(n_iters, B)`` host
+    tensor, and ``stopped_at`` a list of ``B`` entries, ``None`` or the first iteration at which that item's loss or gradient was not
+    finite (such an iteration leaves the item's parameters as they stood and touches no other item).  ``FloatingPointError`` is raised
+    only when every item stopped.  ``pick(result, b)`` is item ``b`` in the form ``optimize`` returns.  ``callback(n, view)`` sees the
+    batched live tensors."""
+    run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
+               batch=batch, batched=True)
+    for n in range(run.n_iters):
+        run.iterate(n)
+    return run.finish()
+
+
+def pick(result, b):
+    """Item ``b`` of an ``optimize_batch`` result as the 8-tuple ``optimize`` returns: ``mix (2, N)``, logits ``(1, T, 27)``,
+    ``(1, 25)``, ``(1, 26)`` (what ``render_blocks`` takes), the dictionaries at batch 1, the history as Python float lists."""
+    mix, lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at = result
+    B = mix.shape[0]
+    b = range(B)[b]  # IndexError for an item that is not there; negative indices count from the end
+
+    def item(v):
+        if isinstance(v, dict):
+            return {k: item(x) for k, x in v.items()}
+        return v[b:b + 1] if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == B else v
+
+    return (mix[b], lt[b:b + 1], item(track_dict), lf[b:b + 1], item(fx_dict), lm[b:b + 1], item(master_dict),
+            {name: h[:, b].tolist() for name, h in loss_history.items()})
 
 
 def render_blocks(tracks, track_params, fx_bus_params, master_bus_params, mix_console, block_size=524288, **console_flags):

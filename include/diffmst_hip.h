@@ -355,6 +355,27 @@ int mst_logit_adam_init(const mst_logit_adam_segment* segments, int32_t n_segmen
 int mst_logit_adam_step(const mst_logit_adam_segment* segments, int32_t n_segments, const float* const* loss_terms, int32_t n_terms,
                         float* history_row, double lr, double beta1, double beta2, double eps, void* state, void* stream);
 
+/* Batched fits: `items` independent optimisations (random restarts, one song against several references, several songs against one)
+ * in ONE launch of `items` workgroups.  Workgroup b is mst_logit_adam_step on item b - the same operations in the same order, so
+ * item b's logits, p, moments, t and history row are bit-identical to a single-song session fed item b's gradients - and exchanges
+ * nothing with the others.
+ *   segments      as above, with `count` the total over all items: it must divide by `items`, and item b owns elements
+ *                 [b count/items, (b + 1) count/items) of theta, p and grad_p - the leading batch dimension of a dense (items, ...) tensor
+ *   state         mst_logit_adam_batch_state_bytes(items, params_per_item) bytes, params_per_item = sum of count/items.  Item b's block
+ *                 starts at int32 word b (16 + 2 params_per_item) and has the layout of the single call: words [0..3] t, status,
+ *                 the iteration that set it, the number of calls; 12 reserved words; item b's first moments in segment order; its
+ *                 second moments.  mst_logit_adam_init_batch zeroes every block and writes p = sigmoid(theta).
+ *   loss_terms    device, dense (items, n_terms) fp32: row b is item b's terms
+ *   history_rows  device, dense (items, 1 + n_terms) fp32: row b is item b's history row of this iteration
+ * A loss term or gradient element of item b that is not finite stops item b's update for this iteration and is recorded in item
+ * b's words [1], [2]; no other item is affected.  1 <= items <= 1024, 1 <= params_per_item <= 2^20: anything else (and every bad
+ * argument of the single call) returns 0 / non-zero before anything is launched. */
+size_t mst_logit_adam_batch_state_bytes(int32_t items, int64_t params_per_item);
+int mst_logit_adam_init_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, void* state, void* stream);
+int mst_logit_adam_step_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, const float* loss_terms,
+                              int32_t n_terms, float* history_rows, double lr, double beta1, double beta2, double eps, void* state,
+                              void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
@@ -406,6 +427,23 @@ int mst_afloss_forward_profile(const float* pred, const double* profile, int32_t
 int mst_afloss_backward_profile(const float* pred, const double* profile, int32_t bs, int64_t n_samples, const float* weights5,
                                 const void* tables, const float* filterbank, const float* grad_losses5, float* grad_pred,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Per-item loss against a profile: row b of `losses` (bs, 5) is the five weighted terms of item b as if it were a batch of one (the
+ * batch divisor of the mean-squared errors is 1, not bs), and row b of `grad_losses` (bs, 5) scales item b's gradient only - what a
+ * batch of independent fits needs (mst_logit_adam_step_batch).  The analysis is that of mst_afloss_forward_profile: the same launches
+ * and the same strip plan at (bs, n_samples); only the epilogues differ (one item per workgroup in the final kernel; the backward
+ * takes the item's cotangent and the divisor 1 where the calls above take one cotangent and bs).  So bs = 1 gives the bits of
+ * mst_afloss_forward_profile / _backward_profile, the mean over the items is the batch call's value to one fp32 rounding, and for a
+ * power-of-two bs the gradient under an all-ones cotangent is exactly bs times the batch call's.  An item never reads another item's
+ * audio, profile row or cotangent.  Workspace: mst_afloss_profile_workspace_bytes(bs, n_samples), the same size as for the batch
+ * calls; the backward follows its forward on the same workspace.  Fixed-order sums, no float atomics: bitwise reproducible.  Bad
+ * arguments return non-zero before anything is launched, as above. */
+int mst_afloss_forward_profile_items(const float* pred, const double* profile, int32_t bs, int64_t n_samples, const float* weights5,
+                                     const void* tables, const float* filterbank, float* losses, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int mst_afloss_backward_profile_items(const float* pred, const double* profile, int32_t bs, int64_t n_samples, const float* weights5,
+                                      const void* tables, const float* filterbank, const float* grad_losses, float* grad_pred,
+                                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Spectrogram encoder: SpectrogramEncoder (reference mst/modules.py:740-806) = STFT front end +
