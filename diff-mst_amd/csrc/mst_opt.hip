@@ -13,6 +13,10 @@
 // loss term; a workgroup-wide flag in LDS carries "something is not finite" to the second pass, which then leaves every coordinate
 // alone (torch would spread the NaN through all of them).  Every lane reads and writes only the coordinates i = tid + k 256 < count of
 // a segment; the history row is written by lane 0, 1 + n_terms floats.
+// The `_best` kernels are the same body with three additions inside the same launch: lane 0 compares the loss sum with the
+// best one in a second caller-owned block and publishes the verdict through LDS at the barrier the step has anyway; on an improvement
+// every lane copies its coordinates of theta into that block BEFORE it updates them (the theta the loss was evaluated at); and an
+// item whose wait count has reached `patience` is marked settled, after which its calls write their history row and nothing else.
 #include <math.h>
 
 #include "mst_common.h"
@@ -23,6 +27,15 @@ constexpr int kOptWG = 256;
 constexpr int kOptHdr = 16;               // int32 words in front of the moments (include/diffmst_hip.h)
 constexpr int64_t kOptMaxParams = 1 << 20;  // per item
 constexpr int kOptMaxItems = 1024;
+constexpr int kBestHdr = 16;  // int32 words in front of the best logits (include/diffmst_hip.h)
+constexpr int kBestSettled = 1, kBestImproved = 2;  // s_best below
+
+// what the `_best` kernels take besides; `block` is NULL in the plain kernels, whose code has none of it (kBest = false)
+struct OptBest {
+    int32_t* block;   // this item's: header, best logits, best history row
+    float min_delta;
+    int32_t patience;
+};
 
 struct OptArgs {
     float* theta[MST_OPT_MAX_SEGMENTS];
@@ -60,15 +73,26 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_batch(OptArgs a, int
     opt_init(a, item, state + (int64_t)item * (kOptHdr + 2 * a.n_params));
 }
 
-// One workgroup's whole step over its item's slices: the body of both kernels below.  term(k) is loss term k of this item, `row` its
-// history row, `state` its block (header, first moments, second moments).
-template <class Term>
+// One workgroup's whole step over its item's slices: the body of the four kernels below.  term(k) is loss term k of this item, `row`
+// its history row, `state` its block (header, first moments, second moments).  kBest adds the best-iterate bookkeeping on `best`;
+// the arithmetic of the update is the same statements either way.
+template <bool kBest, class Term>
 __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, float* __restrict__ row, double lr, double beta1,
-                                         double beta2, float eps, int32_t* __restrict__ state) {
+                                         double beta2, float eps, int32_t* __restrict__ state, OptBest best = OptBest{}) {
     __shared__ int s_bad;
+    __shared__ int s_best;
     __shared__ float s_step, s_c2;
     const int tid = threadIdx.x;
-    if (tid == 0) s_bad = 0;
+    if (tid == 0) {
+        s_bad = 0;
+        if (kBest) {  // the verdict on this iteration's loss, for every lane after the barrier below; it holds only if the step is taken
+            int verdict = best.block[3] ? kBestSettled : 0;
+            float sum = 0.0f;  // the sum lane 0 writes to row[0] below: the same additions in the same order
+            for (int k = 0; k < a.n_terms; ++k) sum += term(k);
+            if (!best.block[0] || sum < __int_as_float(best.block[1]) - best.min_delta) verdict |= kBestImproved;
+            s_best = verdict;
+        }
+    }
     __syncthreads();
     bool bad = false;
 #pragma unroll
@@ -86,7 +110,9 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
         s_c2 = (float)sqrt(1.0 - pow(beta2, t));
     }
     __syncthreads();
+    const bool settled = kBest && (s_best & kBestSettled);
     const bool stop = s_bad != 0;
+    const bool improved = kBest && !stop && (s_best & kBestImproved);  // and not settled: a settled item returns before it is used
     if (tid == 0) {
         float sum = 0.0f;  // the script's `loss = 0; loss += value`, left to right
         for (int k = 0; k < a.n_terms; ++k) {
@@ -96,14 +122,33 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
         }
         row[0] = sum;
         const int32_t iteration = state[3];
-        if (stop && !state[1]) {
-            state[1] = MST_OPT_STATUS_NONFINITE;
-            state[2] = iteration;
+        if (settled) {  // frozen: the row and the call count, nothing else - not even the status of a non-finite input
+            state[3] = iteration + 1;
+        } else {
+            if (stop && !state[1]) {
+                state[1] = MST_OPT_STATUS_NONFINITE;
+                state[2] = iteration;
+            }
+            state[3] = iteration + 1;
+            if (!stop) state[0] += 1;
+            if (kBest && !stop) {  // a non-finite iteration leaves the best block alone, the wait count too
+                int32_t wait = 0;
+                if (improved) {
+                    float* __restrict__ best_row = reinterpret_cast<float*>(best.block + kBestHdr + a.n_params);
+                    best_row[0] = sum;
+                    for (int k = 0; k < a.n_terms; ++k) best_row[1 + k] = term(k);
+                    best.block[0] = iteration + 1;
+                    best.block[1] = __float_as_int(sum);
+                } else {
+                    wait = best.block[2] + 1;
+                }
+                best.block[2] = wait;
+                if (best.patience > 0 && wait >= best.patience) best.block[3] = iteration + 1;  // frozen from the next call on
+            }
         }
-        state[3] = iteration + 1;
-        if (!stop) state[0] += 1;
     }
-    if (stop) return;
+    if (settled || stop) return;
+    float* __restrict__ snap = kBest ? reinterpret_cast<float*>(best.block + kBestHdr) : nullptr;
     const float step = s_step, c2 = s_c2, b2 = (float)beta2, w1 = (float)(1.0 - beta1), w2 = (float)(1.0 - beta2);
     float* __restrict__ m_all = reinterpret_cast<float*>(state + kOptHdr);
     float* __restrict__ v_all = m_all + a.n_params;
@@ -124,12 +169,16 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
                 const float g = (dp[i] * (1.0f - pi)) * pi;
                 const float mi = m[i] + w1 * (g - m[i]);
                 const float vi = v[i] * b2 + (w2 * g) * g;
+                if (improved) snap[at + i] = th[i];  // the logit the loss was evaluated at; this lane is the only one that touches i
                 const float ti = th[i] + (step * mi) / (sqrtf(vi) / c2 + eps);
                 m[i] = mi;
                 v[i] = vi;
                 th[i] = ti;
                 p[i] = opt_sigmoid(ti);
             }
+        } else if (improved) {
+            const float* __restrict__ th = a.theta[s] + (int64_t)item * n;
+            for (int i = tid; i < n; i += kOptWG) snap[at + i] = th[i];
         }
         at += n;
     }
@@ -137,7 +186,7 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
 
 __global__ __launch_bounds__(kOptWG) void k_logit_adam_step(OptArgs a, float* __restrict__ row, double lr, double beta1, double beta2,
                                                             float eps, int32_t* __restrict__ state) {
-    opt_step(a, 0, [&](int k) { return *a.term[k]; }, row, lr, beta1, beta2, eps, state);
+    opt_step<false>(a, 0, [&](int k) { return *a.term[k]; }, row, lr, beta1, beta2, eps, state);
 }
 // Batched fits (include/diffmst_hip.h): workgroup b is the single kernel on item b - its slice of every segment, row b of the dense
 // (items, n_terms) loss terms, history row b, state block b, its own "not finite" flag in its own LDS.  Workgroups exchange nothing.
@@ -146,8 +195,23 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step_batch(OptArgs a, con
                                                                   int32_t* __restrict__ state) {
     const int item = blockIdx.x;
     const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
-    opt_step(a, item, [&](int k) { return mine[k]; }, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
-             state + (int64_t)item * (kOptHdr + 2 * a.n_params));
+    opt_step<false>(a, item, [&](int k) { return mine[k]; }, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+                    state + (int64_t)item * (kOptHdr + 2 * a.n_params));
+}
+// The same two with the best-iterate block (include/diffmst_hip.h): `best.block` is the first item's, item b's lies
+// b (16 + n_params + 1 + MST_OPT_MAX_TERMS) words further.
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best(OptArgs a, float* __restrict__ row, double lr, double beta1,
+                                                                 double beta2, float eps, int32_t* __restrict__ state, OptBest best) {
+    opt_step<true>(a, 0, [&](int k) { return *a.term[k]; }, row, lr, beta1, beta2, eps, state, best);
+}
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_batch(OptArgs a, const float* __restrict__ terms,
+                                                                       float* __restrict__ rows, double lr, double beta1, double beta2,
+                                                                       float eps, int32_t* __restrict__ state, OptBest best) {
+    const int item = blockIdx.x;
+    const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
+    best.block += (int64_t)item * (kBestHdr + a.n_params + 1 + MST_OPT_MAX_TERMS);
+    opt_step<true>(a, item, [&](int k) { return mine[k]; }, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+                   state + (int64_t)item * (kOptHdr + 2 * a.n_params), best);
 }
 
 namespace {
@@ -171,6 +235,13 @@ bool opt_args(const mst_logit_adam_segment* segments, int32_t n_segments, OptArg
     if (total > kOptMaxParams) return false;
     a.n_segments = n_segments;
     a.n_params = (int32_t)total;
+    return true;
+}
+// the extra arguments of the `_best` launchers; false for what they refuse
+bool opt_best(void* best, double min_delta, int32_t patience, OptBest& b) {
+    if (!best || ((uintptr_t)best & 3) || !(min_delta >= 0.0) || !isfinite(min_delta) || !isfinite((float)min_delta) || patience < 0)
+        return false;
+    b = OptBest{(int32_t*)best, (float)min_delta, patience};
     return true;
 }
 }  // namespace
@@ -232,5 +303,44 @@ extern "C" int mst_logit_adam_step_batch(const mst_logit_adam_segment* segments,
     a.n_terms = n_terms;
     hipLaunchKernelGGL(k_logit_adam_step_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms, history_rows, lr,
                        beta1, beta2, (float)eps, (int32_t*)state);
+    return (int)hipGetLastError();
+}
+
+// ---- the same steps, remembering the best iterate and freezing an item that has stopped improving ---------------------------------
+extern "C" size_t mst_logit_adam_best_bytes(int32_t items, int64_t params_per_item) {
+    if (items < 1 || items > kOptMaxItems || params_per_item < 1 || params_per_item > kOptMaxParams) return 0;
+    return (size_t)items * ((size_t)kBestHdr + (size_t)params_per_item + 1 + MST_OPT_MAX_TERMS) * 4;
+}
+extern "C" int mst_logit_adam_step_best(const mst_logit_adam_segment* segments, int32_t n_segments, const float* const* loss_terms,
+                                        int32_t n_terms, float* history_row, double lr, double beta1, double beta2, double eps,
+                                        double min_delta, int32_t patience, void* state, void* best, void* stream) {
+    OptArgs a;
+    OptBest b;
+    if (!opt_args(segments, n_segments, a) || !state || ((uintptr_t)state & 3) || !history_row || ((uintptr_t)history_row & 3) ||
+        !loss_terms || n_terms < 1 || n_terms > MST_OPT_MAX_TERMS)
+        return hipErrorInvalidValue;
+    if (!opt_hyper_ok(lr, beta1, beta2, eps) || !opt_best(best, min_delta, patience, b)) return hipErrorInvalidValue;
+    for (int k = 0; k < n_terms; ++k) {
+        if (!loss_terms[k] || ((uintptr_t)loss_terms[k] & 3)) return hipErrorInvalidValue;
+        a.term[k] = loss_terms[k];
+    }
+    a.n_terms = n_terms;
+    hipLaunchKernelGGL(k_logit_adam_step_best, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, history_row, lr, beta1, beta2,
+                       (float)eps, (int32_t*)state, b);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_logit_adam_step_best_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items,
+                                              const float* loss_terms, int32_t n_terms, float* history_rows, double lr, double beta1,
+                                              double beta2, double eps, double min_delta, int32_t patience, void* state, void* best,
+                                              void* stream) {
+    OptArgs a;
+    OptBest b;
+    if (!opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3) || !history_rows ||
+        ((uintptr_t)history_rows & 3) || !loss_terms || ((uintptr_t)loss_terms & 3) || n_terms < 1 || n_terms > MST_OPT_MAX_TERMS)
+        return hipErrorInvalidValue;
+    if (!opt_hyper_ok(lr, beta1, beta2, eps) || !opt_best(best, min_delta, patience, b)) return hipErrorInvalidValue;
+    a.n_terms = n_terms;
+    hipLaunchKernelGGL(k_logit_adam_step_best_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms, history_rows, lr,
+                       beta1, beta2, (float)eps, (int32_t*)state, b);
     return (int)hipGetLastError();
 }

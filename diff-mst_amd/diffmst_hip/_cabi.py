@@ -121,6 +121,7 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
 OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
 OPT_MAX_ITEMS = 1024  # items of mst_logit_adam_step_batch
 OPT_HEADER_WORDS = 16  # int32 words in front of an item's moments
+OPT_BEST_HEADER_WORDS = 16  # int32 words in front of an item's best logits (mst_logit_adam_step_best)
 AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
 
 
@@ -212,6 +213,11 @@ SIGNATURES = {
     "mst_logit_adam_init_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, _S]),
     "mst_logit_adam_step_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_double,
                                            C.c_double, C.c_double, _P, _S]),
+    "mst_logit_adam_best_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "mst_logit_adam_step_best": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _P, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
+    "mst_logit_adam_step_best_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double,
+                                                C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

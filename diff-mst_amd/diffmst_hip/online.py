@@ -8,18 +8,61 @@ tensors, six ``.item()`` host reads) is ONE launch here, ``mst_logit_adam_step``
 dL/dp through the sigmoid, applies Adam, writes the next iteration's parameters, appends the loss terms to a history on the device and
 keeps the step count there.  The host reads nothing between the first and the last iteration.
 
+``keep_best=True`` returns the best iterate instead of the last, ``patience`` freezes a fit that has stopped improving and ``best_of()``
+picks the best restart of a batch: ``mst_logit_adam_step_best`` / ``_step_best_batch`` keep the best logits in a second block on the
+device inside the same one launch.
+
 PARITY UNPINNED: the script cannot be imported (it imports ``StereoCLAPLoss``, which the reference's ``mst/loss.py`` does not define),
 so its loop is restated here and checked against ``torch.optim.Adam`` behind ``torch.sigmoid`` on recorded gradients.
 """
 from __future__ import annotations
 
 import ctypes
+import struct
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import torch
 
 from . import _cabi, _hip
 from .loss import AudioFeatureProfile
+
+
+class FitReport(NamedTuple):
+    """What ``keep_best=True`` appends to a result: numbers for ``optimize``, lists of ``B`` of them for ``optimize_batch``.
+
+    ``best_iteration`` is the iteration whose loss was the best (``None`` for an item of a batch that never had a finite iteration),
+    ``best_loss`` that loss (``"loss"`` of the history at that iteration; ``inf`` without a best), ``settled_at`` the iteration at
+    which ``patience`` ran out (``None`` if it did not) and ``iterations_run`` the number of iterations the loop ran."""
+    best_iteration: object
+    best_loss: object
+    settled_at: object
+    iterations_run: object
+
+
+def _check_best(keep_best, patience, min_delta, poll_every):
+    """The four keywords of the best-iterate flow -> (patience as the kernel takes it, min_delta, poll_every or None)."""
+    min_delta = float(min_delta)
+    try:
+        finite = 0.0 <= struct.unpack("f", struct.pack("f", min_delta))[0] < float("inf")  # the kernel compares in fp32
+    except OverflowError:
+        finite = False
+    if not finite:
+        raise ValueError(f"min_delta must be a finite fp32 number >= 0, got {min_delta}")
+    if patience is not None:
+        if not keep_best:
+            raise ValueError("patience needs keep_best=True: an item that is frozen is returned at its best iterate")
+        if int(patience) != patience or int(patience) < 0:
+            raise ValueError(f"patience must be a number of iterations >= 0 (0 never freezes), got {patience}")
+    elif min_delta and not keep_best:
+        raise ValueError("min_delta needs keep_best=True")
+    if poll_every is not None:
+        if patience is None:
+            raise ValueError("poll_every needs patience: without it no item ever settles")
+        if int(poll_every) != poll_every or int(poll_every) < 1:
+            raise ValueError(f"poll_every must be a positive number of iterations, got {poll_every}")
+        poll_every = int(poll_every)
+    return (0 if patience is None else int(patience)), min_delta, poll_every
 
 
 def start_point(n_tracks: int, mix_console, init_scale: float = 0.001, generator=None):
@@ -110,7 +153,9 @@ class _Run:
     device), ``iterate(n)`` (nothing in it waits for the device) and ``finish()`` (the one read of history and status)."""
 
     def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-                 batch=None, batched=False):
+                 batch=None, batched=False, keep_best=False, patience=None, min_delta=0.0, poll_every=None):
+        self.keep_best = bool(keep_best)
+        self.patience, self.min_delta, self.poll_every = _check_best(self.keep_best, patience, min_delta, poll_every)
         is_profile = isinstance(ref_mix, AudioFeatureProfile)
         if not is_profile and not isinstance(ref_mix, torch.Tensor):
             raise TypeError(f"ref_mix must be a (2, n_samples) tensor or an AudioFeatureProfile, got {type(ref_mix).__name__}")
@@ -157,8 +202,12 @@ class _Run:
                                 for i in range(3))
         self.params = tuple(torch.empty_like(t).requires_grad_(True) for t in self.logits)  # leaves the kernel rewrites
         self.state = _init(self.logits, self.params, B)
+        self.best = None
+        if self.keep_best:  # all zero: no best yet
+            per_item = sum(t.numel() for t in self.logits) // (B or 1)
+            self.best = torch.zeros(_hip.lib().mst_logit_adam_best_bytes(B or 1, per_item) // 4, dtype=torch.int32, device=dev)
         self.one = torch.ones((), dtype=torch.float32, device=dev)
-        self.keys, self.history, self.result = None, None, None
+        self.keys, self.history, self.result, self.ran = None, None, None, 0
 
     def iterate(self, n):
         lib = _hip.lib()
@@ -189,15 +238,78 @@ class _Run:
         if B is None:
             term_ptrs = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
             with _hip.launch_on(self.tracks.device) as st:
-                lib.mst_logit_adam_step(segments, len(self.logits), term_ptrs, len(terms), row, *self.hyper, self.state, st)
+                if self.keep_best:
+                    lib.mst_logit_adam_step_best(segments, len(self.logits), term_ptrs, len(terms), row, *self.hyper, self.min_delta,
+                                                 self.patience, self.state, self.best, st)
+                else:
+                    lib.mst_logit_adam_step(segments, len(self.logits), term_ptrs, len(terms), row, *self.hyper, self.state, st)
         else:
             dense = torch.stack([t.detach() for t in terms], dim=1)  # (B, n_terms), after the callback: it sees what the callback left
             with _hip.launch_on(self.tracks.device) as st:
-                lib.mst_logit_adam_step_batch(segments, len(self.logits), B, dense, len(terms), row, *self.hyper, self.state, st)
+                if self.keep_best:
+                    lib.mst_logit_adam_step_best_batch(segments, len(self.logits), B, dense, len(terms), row, *self.hyper,
+                                                       self.min_delta, self.patience, self.state, self.best, st)
+                else:
+                    lib.mst_logit_adam_step_batch(segments, len(self.logits), B, dense, len(terms), row, *self.hyper, self.state, st)
+        self.ran = n + 1
+
+    def loop(self):
+        """Every iteration, or with ``poll_every`` until every item is settled or stopped: the read every ``poll_every`` iterations
+        is the one wait the caller asked for."""
+        for n in range(self.n_iters):
+            self.iterate(n)
+            if self.poll_every and (n + 1) % self.poll_every == 0 and self.all_done():
+                break
+        return self.finish()
+
+    def all_done(self):
+        """Every item is settled (best word [3]) or stopped (state word [1]): a read of the device."""
+        B = self.items or 1
+        settled = self.best.view(B, -1)[:, 3]
+        stopped = self.state.view(B, -1)[:, 1]
+        return bool(((settled != 0) | (stopped != 0)).all())
+
+    def _finish_best(self):
+        """The best iterate in place of the last one: its logits out of the best block, its parameters by the init launch (the sigmoid
+        bits the loop used), one console forward under ``no_grad`` -> (mix, logits, dictionaries, report columns, state words)."""
+        B = self.items or 1
+        hdr = _cabi.OPT_BEST_HEADER_WORDS
+        counts = [t.numel() // B for t in self.logits]
+        block = self.best.view(B, -1)
+        words = block[:, :4].tolist()
+        state_words = self.state.view(B, -1)[:, :4].tolist()
+        has_best = [w[0] != 0 for w in words]
+        if not any(has_best):
+            where = [w[2] for w in state_words]
+            raise FloatingPointError(f"{'optimize_batch' if self.items else 'optimize'}: no iteration had a finite loss and gradient "
+                                     f"(first at iteration{'s' if self.items else ''} {where if self.items else where[0]}); the "
+                                     "parameters were left as they stood")
+        stored = block[:, hdr:hdr + sum(counts)].view(torch.float32).split(counts, dim=1)
+        keep = torch.tensor(has_best, device=block.device)
+        # an item without a best iterate never moved: its live logits are its start point
+        logits = tuple(torch.where(keep.view((B,) + (1,) * (live.dim() - 1)), got.reshape(live.shape), live).contiguous()
+                       for got, live in zip(stored, self.logits))
+        with torch.no_grad():
+            params = tuple(torch.empty_like(t) for t in logits)
+            _init(logits, params, self.items)
+            _, mix, track_dict, fx_dict, master_dict = self.console(self.tracks, *params, **self.flags)
+        best_loss = [struct.unpack("f", struct.pack("i", w[1]))[0] if ok else float("inf") for w, ok in zip(words, has_best)]
+        report = FitReport([w[0] - 1 if ok else None for w, ok in zip(words, has_best)], best_loss,
+                           [w[3] - 1 if w[3] else None for w in words], [self.ran] * B)
+        return mix, logits, (track_dict, fx_dict, master_dict), report, state_words
 
     def finish(self):
-        history = self.history.cpu()  # the one wait of the run
+        history = self.history[:self.ran].cpu()  # the one wait of the run
         names = ("loss",) + self.keys
+        if self.keep_best:
+            mix, (lt, lf, lm), (track_dict, fx_dict, master_dict), report, words = self._finish_best()
+            if self.items is not None:
+                stopped_at = [where if status else None for _, status, where, _ in words]
+                loss_history = {name: history[:, :, i].clone() for i, name in enumerate(names)}
+                return mix.detach(), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at, report
+            loss_history = {name: history[:, i].tolist() for i, name in enumerate(names)}
+            return (mix.detach().squeeze(0), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history,
+                    FitReport(*(column[0] for column in report)))
         _, mix, track_dict, fx_dict, master_dict = self.result
         lt, lf, lm = self.logits
         if self.items is not None:
@@ -217,7 +329,7 @@ class _Run:
 
 
 def optimize(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, betas=(0.9, 0.999), eps=1e-8,
-             generator=None, callback=None, **console_flags):
+             generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None, **console_flags):
     """The reference's ``optimize`` (scripts/online.py:15-123): fit the console's parameters to ``ref_mix`` by Adam on their logits.
 
     ``tracks (T, N)`` and ``ref_mix (2, M)`` are device tensors (a CPU tensor raises, as everywhere in this package).  Every iteration
@@ -252,15 +364,27 @@ def optimize(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1
     iteration ``n``; ``view.params``, ``view.grads``, ``view.losses`` and ``view.logits`` are the live tensors (clone what is to be kept;
     a callback that reads values synchronises, which is then the caller's choice).  A console built with ``validate="deferred"`` keeps
     the loop free of host waits; the default ``validate="sync"`` waits for its range check in every forward.
+
+    ``keep_best=True`` returns the BEST iterate instead of the last: Adam with a fixed ``lr`` does not descend monotonically
+    on this loss.  Every iteration is still one launch (``mst_logit_adam_step_best``) and nothing in the loop reads the device: the
+    kernel compares the loss sum with the best so far - an improvement is ``loss < best - min_delta`` in fp32, so a tie keeps the earlier
+    iterate - and on an improvement keeps the logits the loss was evaluated at.  After the loop the best logits become parameters by
+    the init launch and go through one more console forward under ``no_grad``; the tuple then holds the best iterate's ``mix``, logits
+    and dictionaries (``render_blocks(song, *result[1:6:2], console)`` renders the best fit), ``loss_history`` stays the whole run's,
+    and a ninth element is a ``FitReport(best_iteration, best_loss, settled_at, iterations_run)``.  An iteration that was not finite
+    changes nothing, as ever, and no longer raises as long as some iteration has a best to report.  ``patience=k`` (needs
+    ``keep_best``) freezes the fit once ``k`` iterations in a row have not improved: later iterations write their history row and
+    nothing else.  ``poll_every=j`` (needs ``patience``) makes the host read the settled word every ``j`` iterations - a wait the caller
+    asks for - and leave the loop when the fit has settled; the history is as long as the iterations that ran.
     """
-    run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags)
-    for n in range(run.n_iters):
-        run.iterate(n)
-    return run.finish()
+    run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
+               keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every)
+    return run.loop()
 
 
 def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, batch=None, betas=(0.9, 0.999),
-                   eps=1e-8, generator=None, callback=None, **console_flags):
+                   eps=1e-8, generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None,
+                   **console_flags):
     """``B`` independent ``optimize`` runs in the launches of one: random restarts, one song against several references, several songs
     against one reference.  One console forward at batch ``B``, ``loss_function.per_item``, one ``torch.autograd.grad`` with a ones
     cotangent per ``(B,)`` term and one ``mst_logit_adam_step_batch`` per iteration; nothing in the loop waits for the host.
@@ -276,18 +400,26 @@ def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001
     tensor, and ``stopped_at`` a list of ``B`` entries, ``None`` or the first iteration at which that item's loss or gradient was not
     finite (such an iteration leaves the item's parameters as they stood and touches no other item).  ``FloatingPointError`` is raised
     only when every item stopped.  ``pick(result, b)`` is item ``b`` in the form ``optimize`` returns.  ``callback(n, view)`` sees the
-    batched live tensors."""
+    batched live tensors.
+
+    ``keep_best``, ``patience``, ``min_delta`` and ``poll_every`` are ``optimize``'s, per item (``mst_logit_adam_step_best_batch``):
+    every item is returned at its own best iterate, an item whose patience has run out is frozen while the others go on, and with
+    ``poll_every`` the loop ends once every item is settled or stopped.  The ``FitReport`` of lists follows ``stopped_at`` as a tenth
+    element; ``FloatingPointError`` is raised only when no item has a best iterate.  ``best_of(result)`` is the item with the lowest
+    best loss - the random-restart recipe ranks restarts by that, not by the noise of the last step."""
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-               batch=batch, batched=True)
-    for n in range(run.n_iters):
-        run.iterate(n)
-    return run.finish()
+               batch=batch, batched=True, keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every)
+    return run.loop()
 
 
 def pick(result, b):
     """Item ``b`` of an ``optimize_batch`` result as the 8-tuple ``optimize`` returns: ``mix (2, N)``, logits ``(1, T, 27)``,
-    ``(1, 25)``, ``(1, 26)`` (what ``render_blocks`` takes), the dictionaries at batch 1, the history as Python float lists."""
-    mix, lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at = result
+    ``(1, 25)``, ``(1, 26)`` (what ``render_blocks`` takes), the dictionaries at batch 1, the history as Python float lists.  A
+    result of ``keep_best=True`` (one element longer: its ``FitReport``) is taken as well; item ``b``'s report is
+    ``[column[b] for column in result[9]]``."""
+    if len(result) not in (9, 10):
+        raise ValueError(f"pick takes what optimize_batch returns (9 elements, 10 with keep_best), got {len(result)}")
+    mix, lt, track_dict, lf, fx_dict, lm, master_dict, loss_history = result[:8]
     B = mix.shape[0]
     b = range(B)[b]  # IndexError for an item that is not there; negative indices count from the end
 
@@ -298,6 +430,18 @@ def pick(result, b):
 
     return (mix[b], lt[b:b + 1], item(track_dict), lf[b:b + 1], item(fx_dict), lm[b:b + 1], item(master_dict),
             {name: h[:, b].tolist() for name, h in loss_history.items()})
+
+
+def best_of(result):
+    """The item of an ``optimize_batch(..., keep_best=True)`` result with the lowest ``best_loss`` (the first of equals), in
+    ``optimize``'s 8-tuple form: ``pick(result, argmin)``."""
+    if len(result) != 10 or not isinstance(result[9], FitReport):
+        raise ValueError("best_of takes the result of optimize_batch(..., keep_best=True)")
+    report = result[9]
+    ranked = [(loss, b) for b, (loss, at) in enumerate(zip(report.best_loss, report.best_iteration)) if at is not None]
+    if not ranked:
+        raise ValueError("no item has a best iterate")
+    return pick(result, min(ranked)[1])
 
 
 def render_blocks(tracks, track_params, fx_bus_params, master_bus_params, mix_console, block_size=524288, **console_flags):

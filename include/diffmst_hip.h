@@ -376,6 +376,37 @@ int mst_logit_adam_step_batch(const mst_logit_adam_segment* segments, int32_t n_
                               int32_t n_terms, float* history_rows, double lr, double beta1, double beta2, double eps, void* state,
                               void* stream);
 
+/* The same steps, keeping the best iterate on the device and freezing an item that has stopped improving.  Still ONE
+ * launch per call, one workgroup per item, nothing read by the host.  `state` is the block of the calls above, with their layout, set
+ * up by mst_logit_adam_init / _init_batch; none of its reserved words is used.  `best` is a second caller-owned block of
+ * mst_logit_adam_best_bytes(items, params_per_item) bytes (items = 1 for the single call) that the caller fills with zeros: all zero
+ * means "no best yet".  Item b's part starts at int32 word b (16 + params_per_item + 1 + MST_OPT_MAX_TERMS):
+ *   [0] the best iteration + 1, 0 = none     [1] the best loss, fp32 bits     [2] iterations since the last improvement
+ *   [3] the iteration at which the item settled + 1, 0 = still running        [4..15] reserved, left zero
+ *   then params_per_item fp32: the item's logits at the best iteration, in segment order, NULL-gradient segments included
+ *   then 1 + n_terms fp32: that iteration's history row (the block leaves room for 1 + MST_OPT_MAX_TERMS)
+ * One call for one item, with n = state word [3] on entry and L the fp32 loss sum that goes to history_row[0]:
+ *   settled (best[3] != 0)   the history row is written and state word [3] advances; theta, p, the moments, t, the status words and
+ *                            the best block stay as they are
+ *   not finite               exactly the plain step (row written, status recorded, nothing updated); the best block, its wait count
+ *                            included, is not touched
+ *   otherwise                the iteration improves if there is no best yet or L < fl32(best loss - fl32(min_delta)) - one fp32
+ *                            subtraction and a strict <: a loss exactly min_delta below the best is no improvement and a tie keeps the
+ *                            earlier iterate.  On an improvement L, n, the history row and theta AS IT IS BEFORE THIS CALL'S UPDATE (the
+ *                            logits the loss was evaluated at) are stored and the wait count becomes 0; otherwise the wait count grows
+ *                            by one.  Then the update of the plain step, the same operations in the same order: theta, p, the moments,
+ *                            t and the history row are bit-identical to mst_logit_adam_step's on the same inputs.  Then, if
+ *                            patience > 0 and the wait count has reached it, n + 1 goes to [3]: the item is frozen from its next call on.
+ * patience = 0 never freezes.  Refused before anything is launched, besides what the plain calls refuse: a NULL or misaligned `best`,
+ * min_delta negative or not finite (as fp32 too), patience < 0.  mst_logit_adam_best_bytes returns 0 for sizes out of range. */
+size_t mst_logit_adam_best_bytes(int32_t items, int64_t params_per_item);
+int mst_logit_adam_step_best(const mst_logit_adam_segment* segments, int32_t n_segments, const float* const* loss_terms,
+                             int32_t n_terms, float* history_row, double lr, double beta1, double beta2, double eps, double min_delta,
+                             int32_t patience, void* state, void* best, void* stream);
+int mst_logit_adam_step_best_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, const float* loss_terms,
+                                   int32_t n_terms, float* history_rows, double lr, double beta1, double beta2, double eps,
+                                   double min_delta, int32_t patience, void* state, void* best, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
