@@ -248,8 +248,7 @@ __global__ __launch_bounds__(64) void k_af_profile_pack(AfArgs a, double* profil
     else v = (double)a.bark[(int64_t)(a.bs + b) * kAfBands + (tid - 6 - kAfBands)];      // side
     profile[(int64_t)b * kAfProfile + tid] = v;
 }
-__global__ __launch_bounds__(64) void k_af_profile_unpack(AfArgs a, const double* profile) {
-    const int tid = threadIdx.x, b = blockIdx.x;
+__device__ __forceinline__ void af_profile_unpack_row(const AfArgs& a, const double* profile, int b, int tid) {
     if (tid >= kAfProfile) return;
     const double v = profile[(int64_t)b * kAfProfile + tid];
     double* st = a.stats + (int64_t)(a.bs + b) * 8;
@@ -257,6 +256,94 @@ __global__ __launch_bounds__(64) void k_af_profile_unpack(AfArgs a, const double
     else if (tid < 6) { st[4 + 2 * (tid - 4)] = v; st[5 + 2 * (tid - 4)] = 0.0; }
     else if (tid < 6 + kAfBands) a.bark[(int64_t)(2 * a.bs + b) * kAfBands + (tid - 6)] = (float)v;
     else a.bark[(int64_t)(3 * a.bs + b) * kAfBands + (tid - 6 - kAfBands)] = (float)v;
+}
+__global__ __launch_bounds__(64) void k_af_profile_unpack(AfArgs a, const double* profile) {
+    af_profile_unpack_row(a, profile, blockIdx.x, threadIdx.x);
+}
+
+// ---- pooled sections (include/diffmst_hip.h: mst_afloss_forward_profile_pooled) -------------------------------------------------------
+// bs = items * S rows, item-major: the S sections of an item become ONE row of statistics and band energies, and everything after that
+// is the per-item route on `items` rows.  The pooled rows live in a second set of arguments `ap` - a copy of `a` with bs = items,
+// n = S n (the N of the energy-type gradients), div = 1, gstride = 5 and `stats` / `bark` pointing into the half of `bandpart` that a
+// one-set analysis never writes (rows 2 bs .. 4 bs - 1) - in the layout every kernel above reads, so k_af_final_items, af_features,
+// k_af_profile_pack and the unpack run on `ap` as they are.
+//   mean squares  (stats_0[q] + stats_1[q] + ...) / S in float64, sections in order: the mean over all S n samples
+//   peaks         the largest section peak per channel, the first in section order on a tie; the arg-max slot holds s n + i, the sample
+//                 index in the concatenation of the sections (exact in a double)
+//   band energy   (lin_0[j] + lin_1[j] + ...) / S summed in FLOAT64 from the sections' fp32 values, sections in order, rounded to
+//                 fp32 once: S = 1 gives the bits of lin, and S copies of one section give them too (2 x, 3 x, 4 x of an fp32 value
+//                 are exact in float64).  Then logf(. + 1e-8f) as k_af_finish forms it.
+// grid (items), 64 lanes; with a profile the item's target row is unpacked in the same launch.
+__global__ __launch_bounds__(64) void k_af_pool(AfArgs a, AfArgs ap, int S, const double* profile) {
+    const int tid = threadIdx.x, item = blockIdx.x;
+    const int64_t b0 = (int64_t)item * S;
+    if (tid < 2 * kAfBands) {
+        const int which = tid / kAfBands, j = tid % kAfBands;
+        const float* lin = a.bark + ((int64_t)(4 + which) * a.bs + b0) * kAfBands + j;
+        double acc = (double)lin[0];
+        for (int s = 1; s < S; ++s) acc += (double)lin[(int64_t)s * kAfBands];
+        const float lp = (float)(acc / (double)S);
+        const int64_t row = (int64_t)which * ap.bs + item;
+        ap.bark[row * kAfBands + j] = logf(lp + 1e-8f);
+        ap.bark[((int64_t)4 * ap.bs + row) * kAfBands + j] = lp;
+    } else if (tid < 2 * kAfBands + 4) {
+        const int q = tid - 2 * kAfBands;
+        double acc = a.stats[b0 * 8 + q];
+        for (int s = 1; s < S; ++s) acc += a.stats[(b0 + s) * 8 + q];
+        ap.stats[(int64_t)item * 8 + q] = acc / (double)S;
+    } else if (tid < 2 * kAfBands + 6) {
+        const int ch = tid - 2 * kAfBands - 4;
+        double pk = -1.0, at = -1.0;
+        for (int s = 0; s < S; ++s) {
+            const double* st = a.stats + (b0 + s) * 8 + 4 + 2 * ch;
+            if (st[0] > pk) { pk = st[0]; at = (double)((int64_t)s * a.n) + st[1]; }
+        }
+        ap.stats[(int64_t)item * 8 + 4 + 2 * ch] = pk;
+        ap.stats[(int64_t)item * 8 + 5 + 2 * ch] = at;
+    }
+    if (profile) af_profile_unpack_row(ap, profile, item, tid);
+}
+// k_af_coef over the pooled rows: one lane per item; the item's energy-type coefficients (N = S n through ap.n) go to every section's
+// row, the crest-factor delta keeps its index only in the section that holds the pooled peak (-1 elsewhere: no sample matches).
+__global__ __launch_bounds__(64) void k_af_coef_sections(AfArgs a, AfArgs ap, int S) {
+    double part[4] = {0, 0, 0, 0};
+    for (int item = threadIdx.x; item < ap.bs; item += 64) {
+        float c[8];
+        af_features(ap, item, ap.grad_losses + (int64_t)item * ap.gstride, part, c);
+        int64_t at[2];
+        for (int ch = 0; ch < 2; ++ch) at[ch] = (int64_t)ap.stats[(int64_t)item * 8 + 5 + 2 * ch];
+        for (int s = 0; s < S; ++s) {
+            float* o = a.coef + ((int64_t)item * S + s) * 16;
+            o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
+            for (int ch = 0; ch < 2; ++ch) {
+                const bool here = at[ch] >= 0 && at[ch] / a.n == s;
+                o[4 + 2 * ch] = c[4 + 2 * ch];
+                o[5 + 2 * ch] = __int_as_float(here ? (int)(at[ch] % a.n) : -1);
+            }
+        }
+    }
+}
+// k_af_bark_dmag with the item's pooled band energies: every section's cotangent row is the item's c_j with one more factor 1 / S.
+__global__ __launch_bounds__(256) void k_af_bark_dmag_sections(AfArgs a, AfArgs ap, int S) {
+    __shared__ float cj[kAfBands];
+    const int tid = threadIdx.x, s = blockIdx.y;  // s < 2*bs
+    if (tid < kAfBands) {
+        const int item = (s % a.bs) / S;
+        const int64_t row = (int64_t)(s / a.bs) * ap.bs + item;  // the item's pooled mid / side row
+        const float B = ap.bark[row * kAfBands + tid], Bt = ap.bark[((int64_t)2 * ap.bs + row) * kAfBands + tid];
+        const float lin = ap.bark[((int64_t)4 * ap.bs + row) * kAfBands + tid];
+        const float g4 = ap.grad_losses[item * ap.gstride + 4];
+        cj[tid] = g4 * a.weights[4] * 2.0f * (B - Bt) / (2.0f * ap.div * kAfBands) / (lin + 1e-8f) / (float)a.n_frames / (float)S;
+    }
+    __syncthreads();
+    const int k = blockIdx.x * 256 + tid;
+    if (k < kAfBins) {
+        const float* fr = a.fb + (int64_t)k * kAfBands;
+        float v = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kAfBands; ++j) v = fmaf(cj[j], fr[j], v);
+        a.meanmag[(int64_t)(4 * a.bs + s) * kAfBins + k] = v;
+    }
 }
 
 // ---- backward ---------------------------------------------------------------------------------------
@@ -571,5 +658,81 @@ extern "C" int mst_afloss_backward_profile_items(const float* pred, const double
     a.div = 1;
     a.grad_pred = grad_pred;
     af_backward(a, stream);  // reads what mst_afloss_forward_profile_items left in the workspace
+    return (int)hipGetLastError();
+}
+
+// ---- pooled sections: S sections of an item are ONE feature row, one set of five terms, one cotangent row ---------------------------
+namespace {
+struct AfPooled {
+    AfPlan p;
+    AfArgs a, ap;
+    bool ok;
+};
+// `a` is the analysis at bs = items * sections as every call above sets it up; `ap` the pooled rows (k_af_pool), which take
+// 2 items 8 doubles + 8 items 24 floats of the 2 bs 16 24 floats of `bandpart` that a one-set analysis leaves unused
+AfPooled af_pooled(int32_t items, int32_t sections, int64_t n, const float* x, const float* tables, const float* fb, const float* weights,
+                   float* ws, bool backward) {
+    AfPooled r{};
+    if (items < 1 || sections < 1 || (int64_t)items * sections > (1 << 24)) return r;
+    const int bs = items * sections;
+    r.p = af_plan(bs, n, 1, backward);
+    if (!r.p.ok) return r;
+    r.ok = true;
+    if (!ws) return r;  // the size only
+    r.a = af_args(r.p, bs, n, x, nullptr, tables, fb, weights, ws);
+    r.a.div = 1;
+    r.a.gstride = 5;
+    r.ap = r.a;
+    float* spare = r.a.bandpart + (int64_t)2 * bs * kAfBinSlices * kAfBands;
+    r.ap.stats = reinterpret_cast<double*>(spare);
+    r.ap.bark = spare + (int64_t)2 * items * 8 * 2;
+    r.ap.bs = items;
+    r.ap.n = n * sections;
+    return r;
+}
+}  // namespace
+extern "C" int mst_af_profile_pooled(const float* x, int32_t items, int32_t sections, int64_t n_samples, const void* tables,
+                                     const float* filterbank, double* profile, void* workspace, size_t workspace_bytes,
+                                     void* stream_) {
+    const float no_weights[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    const AfPooled r = af_pooled(items, sections, n_samples, x, (const float*)tables, filterbank, no_weights, (float*)workspace, false);
+    if (!r.ok || !x || !tables || !filterbank || !profile || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)r.p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    af_analyse(r.a, stream);
+    hipLaunchKernelGGL(k_af_pool, dim3(items), dim3(64), 0, stream, r.a, r.ap, (int)sections, (const double*)nullptr);
+    hipLaunchKernelGGL(k_af_profile_pack, dim3(items), dim3(64), 0, stream, r.ap, profile);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_afloss_forward_profile_pooled(const float* pred, const double* profile, int32_t items, int32_t sections,
+                                                 int64_t n_samples, const float* weights5, const void* tables, const float* filterbank,
+                                                 float* losses, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!weights5) return hipErrorInvalidValue;
+    AfPooled r = af_pooled(items, sections, n_samples, pred, (const float*)tables, filterbank, weights5, (float*)workspace, true);
+    if (!r.ok || !pred || !profile || !tables || !filterbank || !losses || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)r.p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    r.ap.losses = losses;
+    af_analyse(r.a, stream);
+    hipLaunchKernelGGL(k_af_pool, dim3(items), dim3(64), 0, stream, r.a, r.ap, (int)sections, profile);
+    hipLaunchKernelGGL(k_af_final_items, dim3(items), dim3(64), 0, stream, r.ap);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_afloss_backward_profile_pooled(const float* pred, const double* profile, int32_t items, int32_t sections,
+                                                  int64_t n_samples, const float* weights5, const void* tables, const float* filterbank,
+                                                  const float* grad_losses, float* grad_pred, void* workspace, size_t workspace_bytes,
+                                                  void* stream_) {
+    if (!weights5) return hipErrorInvalidValue;
+    AfPooled r = af_pooled(items, sections, n_samples, pred, (const float*)tables, filterbank, weights5, (float*)workspace, true);
+    if (!r.ok || !pred || !profile || !tables || !filterbank || !grad_losses || !grad_pred || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)r.p.total * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    r.ap.grad_losses = grad_losses;
+    r.a.grad_pred = grad_pred;
+    // reads what mst_afloss_forward_profile_pooled left in the workspace; the adjoint transforms and the gather run per section as ever
+    hipLaunchKernelGGL(k_af_coef_sections, dim3(1), dim3(64), 0, stream, r.a, r.ap, (int)sections);
+    hipLaunchKernelGGL(k_af_bark_dmag_sections, dim3((kAfBins + 255) / 256, 2 * r.a.bs), dim3(256), 0, stream, r.a, r.ap, (int)sections);
+    launch_af2_bark_bwd(r.a, stream);
+    hipLaunchKernelGGL(k_af_bwd_gather, dim3((unsigned)((r.a.n + 1023) / 1024), r.a.bs), dim3(256), 0, stream, r.a);
     return (int)hipGetLastError();
 }

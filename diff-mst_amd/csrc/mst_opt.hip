@@ -67,7 +67,37 @@ __device__ __forceinline__ void opt_init(const OptArgs& a, int item, int32_t* __
         for (int i = tid; i < a.count[s]; i += kOptWG) p[i] = opt_sigmoid(th[i]);
     }
 }
+// The sum of the sections' gradient rows at coordinate i, ((g_0 + g_1) + g_2) + ... in fp32 in section order; `bad` collects an
+// addend or a partial sum that is not finite (two finite addends may overflow).  One row: the element itself, no addition.
+__device__ __forceinline__ float opt_section_sum(const float* __restrict__ dp, int i, int n, int sections, bool& bad) {
+    float sum = dp[i];
+    bad |= !opt_finite(sum);
+    for (int r = 1; r < sections; ++r) {
+        const float g = dp[(int64_t)r * n + i];
+        bad |= !opt_finite(g);
+        sum = sum + g;
+        bad |= !opt_finite(sum);
+    }
+    return sum;
+}
 __global__ __launch_bounds__(kOptWG) void k_logit_adam_init(OptArgs a, int32_t* __restrict__ state) { opt_init(a, 0, state); }
+// ... for one parameter set whose p has `sections` equal rows: the init of the single kernel, its p written to every row
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_init_sections(OptArgs a, int32_t* __restrict__ state, int sections) {
+    const int tid = threadIdx.x;
+    const int words = kOptHdr + 2 * a.n_params;
+    for (int w = tid; w < words; w += kOptWG) state[w] = 0;
+#pragma unroll
+    for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
+        if (s >= a.n_segments) break;
+        const float* __restrict__ th = a.theta[s];
+        float* __restrict__ p = a.p[s];
+        const int n = a.count[s];
+        for (int i = tid; i < n; i += kOptWG) {
+            const float pi = opt_sigmoid(th[i]);
+            for (int r = 0; r < sections; ++r) p[(int64_t)r * n + i] = pi;
+        }
+    }
+}
 __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_batch(OptArgs a, int32_t* __restrict__ state) {
     const int item = blockIdx.x;
     opt_init(a, item, state + (int64_t)item * (kOptHdr + 2 * a.n_params));
@@ -76,9 +106,12 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_batch(OptArgs a, int
 // One workgroup's whole step over its item's slices: the body of the four kernels below.  term(k) is loss term k of this item, `row`
 // its history row, `state` its block (header, first moments, second moments).  kBest adds the best-iterate bookkeeping on `best`;
 // the arithmetic of the update is the same statements either way.
-template <bool kBest, class Term>
+// kSections (mst_logit_adam_step_sections): grad_p and p have `sections` rows of `count`, `count` elements apart; the gradient of a
+// coordinate is the sum of its rows (opt_section_sum) and the new p goes to every row.  Everything else is the same statements.
+template <bool kBest, class Term, bool kSections = false>
 __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, float* __restrict__ row, double lr, double beta1,
-                                         double beta2, float eps, int32_t* __restrict__ state, OptBest best = OptBest{}) {
+                                         double beta2, float eps, int32_t* __restrict__ state, OptBest best = OptBest{},
+                                         int sections = 1) {
     __shared__ int s_bad;
     __shared__ int s_best;
     __shared__ float s_step, s_c2;
@@ -100,7 +133,11 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
         if (s >= a.n_segments) break;
         if (!a.grad_p[s]) continue;
         const float* __restrict__ dp = a.grad_p[s] + (int64_t)item * a.count[s];
-        for (int i = tid; i < a.count[s]; i += kOptWG) bad |= !opt_finite(dp[i]);
+        if (kSections) {
+            for (int i = tid; i < a.count[s]; i += kOptWG) opt_section_sum(dp, i, a.count[s], sections, bad);
+        } else {
+            for (int i = tid; i < a.count[s]; i += kOptWG) bad |= !opt_finite(dp[i]);
+        }
     }
     if (tid < a.n_terms) bad |= !opt_finite(term(tid));
     if (bad) atomicMax(&s_bad, 1);
@@ -165,8 +202,10 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
             float* __restrict__ m = m_all + at;
             float* __restrict__ v = v_all + at;
             for (int i = tid; i < n; i += kOptWG) {
-                const float pi = p[i];
-                const float g = (dp[i] * (1.0f - pi)) * pi;
+                const float pi = p[i];  // with sections: row 0, every row holds the same bits
+                bool ignored = false;
+                const float dpi = kSections ? opt_section_sum(dp, i, n, sections, ignored) : dp[i];
+                const float g = (dpi * (1.0f - pi)) * pi;
                 const float mi = m[i] + w1 * (g - m[i]);
                 const float vi = v[i] * b2 + (w2 * g) * g;
                 if (improved) snap[at + i] = th[i];  // the logit the loss was evaluated at; this lane is the only one that touches i
@@ -174,7 +213,10 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
                 m[i] = mi;
                 v[i] = vi;
                 th[i] = ti;
-                p[i] = opt_sigmoid(ti);
+                const float pn = opt_sigmoid(ti);
+                p[i] = pn;
+                if (kSections)
+                    for (int r = 1; r < sections; ++r) p[(int64_t)r * n + i] = pn;
             }
         } else if (improved) {
             const float* __restrict__ th = a.theta[s] + (int64_t)item * n;
@@ -212,6 +254,19 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_batch(OptArgs a
     best.block += (int64_t)item * (kBestHdr + a.n_params + 1 + MST_OPT_MAX_TERMS);
     opt_step<true>(a, item, [&](int k) { return mine[k]; }, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
                    state + (int64_t)item * (kOptHdr + 2 * a.n_params), best);
+}
+
+// One parameter set, `sections` gradient rows (include/diffmst_hip.h): the single kernels' body on the summed gradient.
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_sections(OptArgs a, float* __restrict__ row, double lr, double beta1,
+                                                                     double beta2, float eps, int32_t* __restrict__ state, int sections) {
+    auto term = [&](int k) { return *a.term[k]; };
+    opt_step<false, decltype(term), true>(a, 0, term, row, lr, beta1, beta2, eps, state, OptBest{}, sections);
+}
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_sections(OptArgs a, float* __restrict__ row, double lr, double beta1,
+                                                                          double beta2, float eps, int32_t* __restrict__ state,
+                                                                          OptBest best, int sections) {
+    auto term = [&](int k) { return *a.term[k]; };
+    opt_step<true, decltype(term), true>(a, 0, term, row, lr, beta1, beta2, eps, state, best, sections);
 }
 
 namespace {
@@ -342,5 +397,39 @@ extern "C" int mst_logit_adam_step_best_batch(const mst_logit_adam_segment* segm
     a.n_terms = n_terms;
     hipLaunchKernelGGL(k_logit_adam_step_best_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms, history_rows, lr,
                        beta1, beta2, (float)eps, (int32_t*)state, b);
+    return (int)hipGetLastError();
+}
+
+// ---- one parameter set, several gradient rows: the sections of a song fitted together ----------------------------------------------
+constexpr int kOptMaxSections = 64;
+extern "C" int mst_logit_adam_init_sections(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t sections, void* state,
+                                            void* stream) {
+    OptArgs a;
+    if (sections < 1 || sections > kOptMaxSections || !opt_args(segments, n_segments, a) || !state || ((uintptr_t)state & 3))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_logit_adam_init_sections, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, (int32_t*)state, (int)sections);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_logit_adam_step_sections(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t sections,
+                                            const float* const* loss_terms, int32_t n_terms, float* history_row, double lr, double beta1,
+                                            double beta2, double eps, double min_delta, int32_t patience, void* state, void* best,
+                                            void* stream) {
+    OptArgs a;
+    OptBest b{};
+    if (sections < 1 || sections > kOptMaxSections || !opt_args(segments, n_segments, a) || !state || ((uintptr_t)state & 3) ||
+        !history_row || ((uintptr_t)history_row & 3) || !loss_terms || n_terms < 1 || n_terms > MST_OPT_MAX_TERMS)
+        return hipErrorInvalidValue;
+    if (!opt_hyper_ok(lr, beta1, beta2, eps) || (best && !opt_best(best, min_delta, patience, b))) return hipErrorInvalidValue;
+    for (int k = 0; k < n_terms; ++k) {
+        if (!loss_terms[k] || ((uintptr_t)loss_terms[k] & 3)) return hipErrorInvalidValue;
+        a.term[k] = loss_terms[k];
+    }
+    a.n_terms = n_terms;
+    if (best)
+        hipLaunchKernelGGL(k_logit_adam_step_best_sections, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, history_row, lr, beta1,
+                           beta2, (float)eps, (int32_t*)state, b, (int)sections);
+    else
+        hipLaunchKernelGGL(k_logit_adam_step_sections, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, history_row, lr, beta1, beta2,
+                           (float)eps, (int32_t*)state, (int)sections);
     return (int)hipGetLastError();
 }

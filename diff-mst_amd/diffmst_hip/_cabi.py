@@ -120,6 +120,7 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
 
 OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
 OPT_MAX_ITEMS = 1024  # items of mst_logit_adam_step_batch
+OPT_MAX_SECTIONS = 64  # sections of mst_logit_adam_step_sections
 OPT_HEADER_WORDS = 16  # int32 words in front of an item's moments
 OPT_BEST_HEADER_WORDS = 16  # int32 words in front of an item's best logits (mst_logit_adam_step_best)
 AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
@@ -218,6 +219,9 @@ SIGNATURES = {
                                           C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
     "mst_logit_adam_step_best_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_double,
                                                 C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
+    "mst_logit_adam_init_sections": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, _S]),
+    "mst_logit_adam_step_sections": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _P,
+                                              C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
@@ -240,6 +244,11 @@ SIGNATURES = {
     "mst_afloss_forward_profile_items": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_afloss_backward_profile_items": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t,
                                                    _S]),
+    "mst_af_profile_pooled": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_afloss_forward_profile_pooled": (STATUS, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P,
+                                                   C.c_size_t, _S]),
+    "mst_afloss_backward_profile_pooled": (STATUS, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P,
+                                                    C.c_size_t, _S]),
     "mst_ctrl_workspace_bytes": (C.c_size_t, [C.POINTER(CtrlDesc)]),
     "mst_ctrl_forward": (STATUS, [C.POINTER(CtrlDesc), _P, _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),
     "mst_ctrl_backward": (STATUS, [C.POINTER(CtrlDesc), _P, C.POINTER(CtrlLayer), _P, C.POINTER(CtrlLayer), _P, _P, C.c_size_t, _S]),

@@ -351,6 +351,42 @@ class _AudioFeatureItemsFunction(torch.autograd.Function):
         return gx.view(shape), None, None, None
 
 
+class _AudioFeaturePooledFunction(torch.autograd.Function):
+    """The loss of the rows of ``pred`` TAKEN TOGETHER against one profile row: five ``(1,)`` outputs, one cotangent row."""
+
+    @staticmethod
+    def forward(ctx, pred, profile, weights, sample_rate):
+        lib = _hip.lib()
+        x = pred.float().contiguous()
+        sections, _, n = x.shape
+        dev = x.device
+        tables, fb = _af_constants(dev, sample_rate)
+        nbytes = lib.mst_afloss_profile_workspace_bytes(sections, n)
+        if nbytes == 0:
+            raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        losses = torch.empty(1, 5, dtype=torch.float32, device=dev)
+        w = (ctypes.c_float * 5)(*[float(v) for v in weights])
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_forward_profile_pooled(x, profile, 1, sections, n, w, tables, fb, losses, ws, nbytes, st)
+        ctx.meta = (sections, n, w, nbytes, pred.shape)
+        ctx.save_for_backward(x, profile, tables, fb, ws)
+        return tuple(losses.unbind(1))  # five (1,) views of one buffer
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_each):
+        x, profile, tables, fb, ws = ctx.saved_tensors
+        sections, n, w, nbytes, shape = ctx.meta
+        lib = _hip.lib()
+        dev = x.device
+        g = torch.stack([gi.float().reshape(1) for gi in grad_each], dim=1).contiguous()  # (1, 5)
+        gx = torch.empty_like(x)
+        with _hip.launch_on(dev) as st:
+            lib.mst_afloss_backward_profile_pooled(x, profile, 1, sections, n, w, tables, fb, g, gx, ws, nbytes, st)
+        return gx.view(shape), None, None, None
+
+
 class AudioFeatureLoss(torch.nn.Module):
     """Drop-in for reference ``mst.loss.AudioFeatureLoss`` (:198-260).
 
@@ -378,9 +414,13 @@ class AudioFeatureLoss(torch.nn.Module):
     Profile = AudioFeatureProfile  # reachable wherever this class is: ``mst.loss.AudioFeatureLoss.Profile`` after ``install()``
 
     @torch.no_grad()
-    def profile(self, x: torch.Tensor) -> AudioFeatureProfile:
+    def profile(self, x: torch.Tensor, pool: bool = False) -> AudioFeatureProfile:
         """Analyse ``x (bs, 2, n)``, ``n > 16384``, on its device -> ``AudioFeatureProfile``.  No gradient reaches ``x``: the target
-        side of this loss never receives one."""
+        side of this loss never receives one.
+
+        ``pool=True``: the rows of ``x`` are sections of ONE signal and the result is one profile of batch size 1, pooled over them as
+        ``pooled`` pools its input (``include/diffmst_hip.h``, ``mst_af_profile_pooled``): rms, crest factor, width and imbalance of the
+        concatenation, the mean magnitude spectrum over all frames of all sections.  For a reference given as sections."""
         _hip.require_cuda(x)
         _af_check_input(x, "signal")
         lib = _hip.lib()
@@ -392,10 +432,42 @@ class AudioFeatureLoss(torch.nn.Module):
             raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
         tables, fb = _af_constants(dev, self.sample_rate)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        data = torch.empty(bs, _cabi.AF_PROFILE_DOUBLES, dtype=torch.float64, device=dev)
+        data = torch.empty(1 if pool else bs, _cabi.AF_PROFILE_DOUBLES, dtype=torch.float64, device=dev)
         with _hip.launch_on(dev) as st:
-            lib.mst_af_profile(x, bs, n, tables, fb, data, ws, nbytes, st)
-        return AudioFeatureProfile(data, self.sample_rate, n)
+            if pool:
+                lib.mst_af_profile_pooled(x, 1, bs, n, tables, fb, data, ws, nbytes, st)
+            else:
+                lib.mst_af_profile(x, bs, n, tables, fb, data, ws, nbytes, st)
+        return AudioFeatureProfile(data, self.sample_rate, bs * n if pool else n)
+
+    def pooled(self, input: torch.Tensor, target):
+        """The five terms of the rows of ``input (S, 2, n)`` TAKEN TOGETHER - S sections of one mix as one signal:
+        ``{key: (1,) float32 device tensor}``, differentiable in ``input``.  All five features are aggregates over time, so the features
+        of several sections are formed from the sections' sums, peaks and mean magnitudes before the nonlinear maps
+        (``mst_afloss_forward_profile_pooled``): rms, crest factor, width and imbalance are those of ``torch.cat(sections, dim=-1)``,
+        the Bark spectrum that of the mean magnitude over all frames of all sections.  This is not the mean of ``per_item``'s rows: the mean of
+        S crest factors is not the crest factor of the whole.  ``S = 1`` is ``per_item`` at batch 1, bit for bit.
+
+        ``target`` is an ``AudioFeatureProfile`` of batch size 1 or a ``(1, 2, m)`` tensor of any length ``m > 16384``, which is
+        profiled on the way.  Errors as ``per_item``'s."""
+        is_profile = isinstance(target, AudioFeatureProfile)
+        if not is_profile and not isinstance(target, torch.Tensor):
+            raise TypeError(f"AudioFeatureLoss takes a tensor or an AudioFeatureProfile as target, got {type(target).__name__}")
+        _hip.require_cuda(input, target.data if is_profile else target)
+        _af_check_input(input, "input")
+        if is_profile:
+            if target.sample_rate != self.sample_rate:
+                raise ValueError(f"the profile was taken at {target.sample_rate} Hz, this loss runs at {self.sample_rate} Hz")
+        else:
+            _af_check_input(target, "target")
+        have = target.batch_size if is_profile else target.shape[0]
+        if have != 1:
+            raise ValueError(f"the sections of the input are pooled into one row, the target has batch size {have}")
+        if not is_profile:
+            target = self.profile(target)
+        _hip.require_same_device(input.device, target.data)
+        losses = _AudioFeaturePooledFunction.apply(input, target.data, tuple(self.weights), self.sample_rate)
+        return dict(zip(AF_KEYS, losses))
 
     def per_item(self, input: torch.Tensor, target):
         """The five terms of every batch item on its own: ``{key: (bs,) float32 device tensor}``, row ``b`` what ``forward`` returns for

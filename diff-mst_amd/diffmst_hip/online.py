@@ -82,9 +82,9 @@ def _segments(logits, params, grads):
     return seg
 
 
-def _init(logits, params, items=None):
+def _init(logits, params, items=None, sections=None):
     """p <- sigmoid(logits) by the kernel every later p comes from, and a zeroed optimiser state: one block, or with ``items`` one
-    block per item of the leading dimension."""
+    block per item of the leading dimension.  With ``sections`` one block, and ``params`` has that many equal rows per logit row."""
     lib = _hip.lib()
     dev = logits[0].device
     total = sum(t.numel() for t in logits)
@@ -97,7 +97,9 @@ def _init(logits, params, items=None):
         raise ValueError(f"more parameters per fit than the logit-Adam kernel takes (2^20), or more than {_cabi.OPT_MAX_ITEMS} fits")
     state = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     with _hip.launch_on(dev) as st:
-        if items is None:
+        if sections is not None:
+            lib.mst_logit_adam_init_sections(_segments(logits, params, none), len(logits), sections, state, st)
+        elif items is None:
             lib.mst_logit_adam_init(_segments(logits, params, none), len(logits), state, st)
         else:
             lib.mst_logit_adam_init_batch(_segments(logits, params, none), len(logits), items, state, st)
@@ -148,18 +150,41 @@ def _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch):
     return B, scales
 
 
+def _check_sections(tracks, ref_mix, is_profile, loss_function):
+    """Types and shapes of ``optimize_sections``, before anything touches the device -> S."""
+    if not callable(getattr(loss_function, "pooled", None)):
+        raise TypeError("optimize_sections needs a loss_function with a pooled(input, target) method (AudioFeatureLoss.pooled): "
+                        f"{type(loss_function).__name__} has none")
+    if not isinstance(tracks, torch.Tensor) or tracks.dim() != 3:
+        raise ValueError("tracks must be (S, n_tracks, n_samples): S sections of one song (take_sections cuts them)")
+    S = tracks.shape[0]
+    if not 1 <= S <= _cabi.OPT_MAX_SECTIONS:
+        raise ValueError(f"the number of sections must be 1..{_cabi.OPT_MAX_SECTIONS}, got {S}")
+    if is_profile:
+        if ref_mix.batch_size != 1:
+            raise ValueError(f"a profile given as ref_mix must have batch size 1, got {ref_mix.batch_size}")
+    elif not (ref_mix.dim() == 2 and ref_mix.shape[0] == 2) and not (ref_mix.dim() == 3 and ref_mix.shape[1] == 2):
+        raise ValueError("ref_mix must be (2, n_samples), (R, 2, n_samples) - R sections of one reference - or an "
+                         f"AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+    _hip.require_cuda(tracks, ref_mix.data if is_profile else ref_mix)
+    return S
+
+
 class _Run:
     """One optimisation, or with ``batch`` a batch of independent ones in the same launches: set-up (the start point goes to the
     device), ``iterate(n)`` (nothing in it waits for the device) and ``finish()`` (the one read of history and status)."""
 
     def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-                 batch=None, batched=False, keep_best=False, patience=None, min_delta=0.0, poll_every=None):
+                 batch=None, batched=False, keep_best=False, patience=None, min_delta=0.0, poll_every=None, sectioned=False):
         self.keep_best = bool(keep_best)
         self.patience, self.min_delta, self.poll_every = _check_best(self.keep_best, patience, min_delta, poll_every)
         is_profile = isinstance(ref_mix, AudioFeatureProfile)
         if not is_profile and not isinstance(ref_mix, torch.Tensor):
             raise TypeError(f"ref_mix must be a (2, n_samples) tensor or an AudioFeatureProfile, got {type(ref_mix).__name__}")
-        if batched:
+        self.sections = None  # S: one parameter set fitted to S sections in the launches of one (optimize_sections)
+        if sectioned:
+            self.items, self.sections = None, _check_sections(tracks, ref_mix, is_profile, loss_function)
+        elif batched:
             self.items, scales = _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch)
         else:
             self.items = _check_single(tracks, ref_mix, is_profile)
@@ -172,12 +197,18 @@ class _Run:
         self.flags = dict(use_fx_bus=False)
         self.flags.update(console_flags)
         n_tracks, n_samples = tracks.shape[-2:]
-        if B is None:
+        if self.sections is not None:
+            self.tracks = tracks.detach()
+        elif B is None:
             self.tracks = tracks.detach().unsqueeze(0)
         else:
             self.tracks = tracks.detach() if tracks.dim() == 3 else tracks.detach().unsqueeze(0).repeat(B, 1, 1)
         if is_profile:
             self.ref_mix = ref_mix
+        elif self.sections is not None:
+            # the pooled loss has no paired route: the reference is analysed here, once - its sections pooled if it comes as sections
+            ref = ref_mix.detach()
+            self.ref_mix = loss_function.profile(ref, pool=True) if ref.dim() == 3 else loss_function.profile(ref.unsqueeze(0))
         else:
             self.ref_mix = ref_mix.detach()
             if self.ref_mix.dim() == 2:
@@ -200,8 +231,12 @@ class _Run:
             draws = [start_point(n_tracks, mix_console, scale, generator) for scale in scales]
             self.logits = tuple(torch.stack([d[i] if i == 0 else d[i][0] for d in draws]).to(device=dev, dtype=torch.float32).contiguous()
                                 for i in range(3))
-        self.params = tuple(torch.empty_like(t).requires_grad_(True) for t in self.logits)  # leaves the kernel rewrites
-        self.state = _init(self.logits, self.params, B)
+        if self.sections is None:
+            self.params = tuple(torch.empty_like(t).requires_grad_(True) for t in self.logits)  # leaves the kernel rewrites
+        else:  # (S, T, 27), (S, 25), (S, 26) leaves whose rows the kernel keeps equal: the console runs at batch S
+            self.params = tuple(torch.empty((self.sections,) + t.shape[1:], dtype=t.dtype, device=dev).requires_grad_(True)
+                                for t in self.logits)
+        self.state = _init(self.logits, self.params, B, self.sections)
         self.best = None
         if self.keep_best:  # all zero: no best yet
             per_item = sum(t.numel() for t in self.logits) // (B or 1)
@@ -213,7 +248,10 @@ class _Run:
         lib = _hip.lib()
         B = self.items
         self.result = result = self.console(self.tracks, *self.params, **self.flags)
-        losses = (self.loss_function if B is None else self.loss_function.per_item)(result[1], self.ref_mix)
+        if self.sections is not None:
+            losses = self.loss_function.pooled(result[1], self.ref_mix)
+        else:
+            losses = (self.loss_function if B is None else self.loss_function.per_item)(result[1], self.ref_mix)
         keys, terms = (tuple(losses), list(losses.values())) if isinstance(losses, dict) else ((), [losses])
         if self.keys is None:
             if not 1 <= len(terms) <= _cabi.OPT_MAX_TERMS:
@@ -238,7 +276,10 @@ class _Run:
         if B is None:
             term_ptrs = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
             with _hip.launch_on(self.tracks.device) as st:
-                if self.keep_best:
+                if self.sections is not None:  # the S gradient rows are summed inside the step
+                    lib.mst_logit_adam_step_sections(segments, len(self.logits), self.sections, term_ptrs, len(terms), row, *self.hyper,
+                                                     self.min_delta, self.patience, self.state, self.best, st)
+                elif self.keep_best:
                     lib.mst_logit_adam_step_best(segments, len(self.logits), term_ptrs, len(terms), row, *self.hyper, self.min_delta,
                                                  self.patience, self.state, self.best, st)
                 else:
@@ -290,8 +331,9 @@ class _Run:
         logits = tuple(torch.where(keep.view((B,) + (1,) * (live.dim() - 1)), got.reshape(live.shape), live).contiguous()
                        for got, live in zip(stored, self.logits))
         with torch.no_grad():
-            params = tuple(torch.empty_like(t) for t in logits)
-            _init(logits, params, self.items)
+            rows = (lambda t: t.shape) if self.sections is None else (lambda t: (self.sections,) + t.shape[1:])
+            params = tuple(torch.empty(rows(t), dtype=t.dtype, device=t.device) for t in logits)
+            _init(logits, params, self.items, self.sections)
             _, mix, track_dict, fx_dict, master_dict = self.console(self.tracks, *params, **self.flags)
         best_loss = [struct.unpack("f", struct.pack("i", w[1]))[0] if ok else float("inf") for w, ok in zip(words, has_best)]
         report = FitReport([w[0] - 1 if ok else None for w, ok in zip(words, has_best)], best_loss,
@@ -308,6 +350,8 @@ class _Run:
                 loss_history = {name: history[:, :, i].clone() for i, name in enumerate(names)}
                 return mix.detach(), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at, report
             loss_history = {name: history[:, i].tolist() for i, name in enumerate(names)}
+            if self.sections is not None:
+                mix = mix.unsqueeze(0)  # squeezed again below: (S, 2, n)
             return (mix.detach().squeeze(0), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history,
                     FitReport(*(column[0] for column in report)))
         _, mix, track_dict, fx_dict, master_dict = self.result
@@ -321,6 +365,8 @@ class _Run:
             loss_history = {name: history[:, :, i].clone() for i, name in enumerate(names)}
             return mix.detach(), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at
         t, status, where, _ = self.state[:4].tolist()
+        if self.sections is not None:
+            mix = mix.unsqueeze(0)  # squeezed again below: (S, 2, n)
         if status:
             raise FloatingPointError(f"optimize: a loss term or a gradient was not finite at iteration {where}; the parameters were "
                                      f"left as they stood ({t} updates applied)")
@@ -409,6 +455,43 @@ def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001
     best loss - the random-restart recipe ranks restarts by that, not by the noise of the last step."""
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
                batch=batch, batched=True, keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every)
+    return run.loop()
+
+
+def take_sections(tracks, starts, length):
+    """``tracks (T, N)`` -> the contiguous ``(S, T, length)`` tensor of the sections ``tracks[:, start:start + length]``, one per entry
+    of ``starts``, on the device of ``tracks``: what ``optimize_sections`` takes."""
+    if not isinstance(tracks, torch.Tensor) or tracks.dim() != 2:
+        raise ValueError("tracks must be (n_tracks, n_samples)")
+    starts, length = [int(v) for v in starts], int(length)
+    if not starts or length < 1:
+        raise ValueError("take_sections needs at least one start and a positive length")
+    for start in starts:
+        if start < 0 or start + length > tracks.shape[1]:
+            raise ValueError(f"the section [{start}, {start + length}) does not lie inside the {tracks.shape[1]} samples of the tracks")
+    return torch.stack([tracks[:, start:start + length] for start in starts]).contiguous()
+
+
+def optimize_sections(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, betas=(0.9, 0.999),
+                      eps=1e-8, generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None,
+                      **console_flags):
+    """``optimize`` for ONE set of console parameters seen through ``S`` sections of the song at once: ``tracks`` is
+    ``(S, T, n)`` (``take_sections``), the console runs at batch ``S`` with parameter leaves ``(S, T, 27)``, ``(S, 25)``, ``(S, 26)``
+    whose rows are equal, ``loss_function.pooled(mix, target)`` turns the ``S`` rendered sections into ONE feature vector and one set
+    of terms, autograd hands back ``(S, ...)`` gradients and ``mst_logit_adam_step_sections`` sums them in section order inside the one
+    step launch - no ``expand``, no copy, no sum on the host.  The parameters that come out are applied to the whole song
+    (``render_blocks``), so what they are fitted to should not be one verse: a crest factor, a stereo width or a Bark spectrum over
+    several sections is compared with a target profile that was pooled over a whole reference.
+
+    ``ref_mix`` is ``(2, M)``, ``(R, 2, M)`` - ``R`` sections of one reference, pooled - or an ``AudioFeatureProfile`` of batch size 1;
+    a tensor is analysed once, before the loop.  ``loss_function`` must offer ``pooled`` (``AudioFeatureLoss``): anything else raises
+    ``TypeError``.  The keywords are ``optimize``'s, ``keep_best``, ``patience``, ``min_delta``, ``poll_every`` and ``callback``
+    included (``view.params`` and ``view.grads`` have ``S`` rows).  The start point is ``optimize``'s.
+
+    Returns ``optimize``'s tuple with ``mix (S, 2, n)``, the dictionaries at batch ``S`` and the logits in ``optimize``'s shapes
+    ``(1, T, 27)``, ``(1, 25)``, ``(1, 26)``, ready for ``render_blocks``.  ``S = 1`` against a profile is ``optimize`` bit for bit."""
+    run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
+               keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every, sectioned=True)
     return run.loop()
 
 

@@ -407,6 +407,25 @@ int mst_logit_adam_step_best_batch(const mst_logit_adam_segment* segments, int32
                                    int32_t n_terms, float* history_rows, double lr, double beta1, double beta2, double eps,
                                    double min_delta, int32_t patience, void* state, void* best, void* stream);
 
+/* One parameter set fitted to SEVERAL SECTIONS of a song at once: the console runs at batch `sections` with parameter
+ * leaves whose rows are equal, autograd hands back one gradient row per section, and the step sums them.  Per segment `theta` has
+ * `count` elements as above, while `p` and `grad_p` are dense (sections, count): row r starts r * count elements in.
+ *   mst_logit_adam_init_sections  zeroes the state block and writes sigmoid(theta) to EVERY row of p
+ *   mst_logit_adam_step_sections  dp[i] = ((g_0[i] + g_1[i]) + g_2[i]) + ... in fp32 in row order, then the step of
+ *                                 mst_logit_adam_step on dp - the same operations in the same order, reading p from row 0 - and the
+ *                                 new p[i] written to every row.  A NULL grad_p keeps theta, the moments and all rows of p.
+ * A gradient element OR a partial sum that is not finite (two finite addends may overflow) stops the iteration exactly as a non-finite
+ * gradient stops mst_logit_adam_step.  `best` NULL: the plain step, min_delta and patience are not looked at.  `best` non-NULL: the
+ * step of mst_logit_adam_step_best with that block, min_delta and patience.  state and best keep the single call's layouts and sizes:
+ * mst_logit_adam_state_bytes(sum of the counts), mst_logit_adam_best_bytes(1, sum of the counts).  sections = 1 gives the bits of
+ * mst_logit_adam_init / _step / _step_best in every output.  One workgroup, one launch, no host synchronisation.  sections outside
+ * [1, 64] and every bad argument of the single calls return non-zero before anything is launched. */
+int mst_logit_adam_init_sections(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t sections, void* state,
+                                 void* stream);
+int mst_logit_adam_step_sections(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t sections,
+                                 const float* const* loss_terms, int32_t n_terms, float* history_row, double lr, double beta1, double beta2,
+                                 double eps, double min_delta, int32_t patience, void* state, void* best, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
@@ -475,6 +494,42 @@ int mst_afloss_forward_profile_items(const float* pred, const double* profile, i
 int mst_afloss_backward_profile_items(const float* pred, const double* profile, int32_t bs, int64_t n_samples, const float* weights5,
                                       const void* tables, const float* filterbank, const float* grad_losses, float* grad_pred,
                                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Pooled sections: S sections of one signal are ONE feature row.  All five features are aggregates over time, so the
+ * features of several sections taken together are formed from what the analysis leaves per section, before the nonlinear maps.
+ * pred / x is (items * sections, 2, n_samples), item-major: row item * sections + s is section s of `item`; all sections share one
+ * length.  Per item, from the per-section statistics and linear band energies:
+ *   mean squares   (m_0 + m_1 + ... + m_{S-1}) / S in float64 in section order: the mean over all S n_samples samples
+ *   peaks          the largest section peak per channel; its arg-max is a (section, sample) pair, the first in section order, then in
+ *                  time order - a tie goes to the earlier section
+ *   Bark bands     lin[j] = (lin_0[j] + ... + lin_{S-1}[j]) / S per signal (mid, side): the mean magnitude over all frames of all
+ *                  sections (every section has the same frame count and keeps its own reflect padding), then log(lin + 1e-8).  The sum
+ *                  is formed in FLOAT64 from the sections' fp32 values and rounded to fp32 once, so S = 1 gives the bits of lin.
+ * In the reference's words: rms, crest factor, width and imbalance are those of torch.cat(sections, dim=-1), and the Bark term is
+ * log(mean_s(exp(compute_barkspectrum(section_s)) - 1e-8) + 1e-8).
+ *   mst_af_profile_pooled               x -> profile (items, 54): the pooled row in the profile layout above; items*54 doubles written
+ *   mst_afloss_forward_profile_pooled   losses (items, 5): the five weighted terms of item's pooled row against profile row `item`,
+ *                                       each item a batch of one as in the _items call
+ *   mst_afloss_backward_profile_pooled  grad_losses (items, 5) -> grad_pred (items * sections, 2, n_samples): every section gets the
+ *                                       item's energy-type coefficients with N = S n_samples; the crest-factor delta lands on the one
+ *                                       (section, sample) that holds the pooled peak; every section's mean-magnitude cotangent is the
+ *                                       item's, formed from the pooled lin, with one more factor 1 / S; the adjoint transforms and the
+ *                                       overlap-add then run per section as in every other backward
+ * The analysis is that of the _items calls at bs = items * sections - the same launches and strip plan - followed by one pooling
+ * launch; the workspace is mst_afloss_profile_workspace_bytes(items * sections, n_samples) for the loss and
+ * mst_af_profile_workspace_bytes(items * sections, n_samples) for the profile (the pooled rows use a part of it that a one-set
+ * analysis leaves unused).  sections = 1 gives the bits of the _items calls and of mst_af_profile; the loss of sections against their own
+ * pooled profile is exactly 0 in all five terms; an item never reads another item's audio, profile row or cotangent.  Fixed-order
+ * sums, no float atomics: bitwise reproducible; every buffer is written exactly up to its count.  items < 1, sections < 1,
+ * n_samples <= 16384, a NULL pointer or a workspace that is too small return non-zero before anything is launched. */
+int mst_af_profile_pooled(const float* x, int32_t items, int32_t sections, int64_t n_samples, const void* tables,
+                          const float* filterbank, double* profile, void* workspace, size_t workspace_bytes, void* stream);
+int mst_afloss_forward_profile_pooled(const float* pred, const double* profile, int32_t items, int32_t sections, int64_t n_samples,
+                                      const float* weights5, const void* tables, const float* filterbank, float* losses, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int mst_afloss_backward_profile_pooled(const float* pred, const double* profile, int32_t items, int32_t sections, int64_t n_samples,
+                                       const float* weights5, const void* tables, const float* filterbank, const float* grad_losses,
+                                       float* grad_pred, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Spectrogram encoder: SpectrogramEncoder (reference mst/modules.py:740-806) = STFT front end +
