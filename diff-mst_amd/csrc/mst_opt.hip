@@ -102,12 +102,34 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_batch(OptArgs a, int
     const int item = blockIdx.x;
     opt_init(a, item, state + (int64_t)item * (kOptHdr + 2 * a.n_params));
 }
+// ... for `items` parameter sets with `sections` equal rows of p each: workgroup b is the sections init on item b - its slice of
+// theta, its state block, rows [b sections, (b + 1) sections) of p
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_init_sections_batch(OptArgs a, int32_t* __restrict__ state, int sections) {
+    const int tid = threadIdx.x;
+    const int item = blockIdx.x;
+    const int words = kOptHdr + 2 * a.n_params;
+    state += (int64_t)item * words;
+    for (int w = tid; w < words; w += kOptWG) state[w] = 0;
+#pragma unroll
+    for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
+        if (s >= a.n_segments) break;
+        const int n = a.count[s];
+        const float* __restrict__ th = a.theta[s] + (int64_t)item * n;
+        float* __restrict__ p = a.p[s] + (int64_t)item * sections * n;
+        for (int i = tid; i < n; i += kOptWG) {
+            const float pi = opt_sigmoid(th[i]);
+            for (int r = 0; r < sections; ++r) p[(int64_t)r * n + i] = pi;
+        }
+    }
+}
 
 // One workgroup's whole step over its item's slices: the body of the four kernels below.  term(k) is loss term k of this item, `row`
 // its history row, `state` its block (header, first moments, second moments).  kBest adds the best-iterate bookkeeping on `best`;
 // the arithmetic of the update is the same statements either way.
 // kSections (mst_logit_adam_step_sections): grad_p and p have `sections` rows of `count`, `count` elements apart; the gradient of a
 // coordinate is the sum of its rows (opt_section_sum) and the new p goes to every row.  Everything else is the same statements.
+// With kSections an item's rows of p and grad_p begin item * sections * count in (mst_logit_adam_step_sections_batch); the single
+// kernels run it with item = 0, where that is no offset at all.
 template <bool kBest, class Term, bool kSections = false>
 __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, float* __restrict__ row, double lr, double beta1,
                                          double beta2, float eps, int32_t* __restrict__ state, OptBest best = OptBest{},
@@ -132,7 +154,8 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
     for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
         if (s >= a.n_segments) break;
         if (!a.grad_p[s]) continue;
-        const float* __restrict__ dp = a.grad_p[s] + (int64_t)item * a.count[s];
+        // an item's rows of grad_p (and of p below) lie item * sections * count in; its theta item * count
+        const float* __restrict__ dp = a.grad_p[s] + (kSections ? (int64_t)item * sections * a.count[s] : (int64_t)item * a.count[s]);
         if (kSections) {
             for (int i = tid; i < a.count[s]; i += kOptWG) opt_section_sum(dp, i, a.count[s], sections, bad);
         } else {
@@ -196,9 +219,10 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
         const int n = a.count[s];
         if (a.grad_p[s]) {  // a NULL gradient is a parameter without .grad: torch skips it, its logits, moments and p keep their bits
             const int64_t off = (int64_t)item * n;
-            const float* __restrict__ dp = a.grad_p[s] + off;
+            const int64_t rows = kSections ? off * sections : off;  // where this item's rows of p and grad_p begin
+            const float* __restrict__ dp = a.grad_p[s] + rows;
             float* __restrict__ th = a.theta[s] + off;
-            float* __restrict__ p = a.p[s] + off;
+            float* __restrict__ p = a.p[s] + rows;
             float* __restrict__ m = m_all + at;
             float* __restrict__ v = v_all + at;
             for (int i = tid; i < n; i += kOptWG) {
@@ -267,6 +291,29 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_sections(OptArg
                                                                           OptBest best, int sections) {
     auto term = [&](int k) { return *a.term[k]; };
     opt_step<true, decltype(term), true>(a, 0, term, row, lr, beta1, beta2, eps, state, best, sections);
+}
+// `items` parameter sets with `sections` gradient rows each (include/diffmst_hip.h): workgroup b is the sections kernel on item b,
+// with the batch kernels' row b of the dense loss terms, history row b, state block b and best block b.  Workgroups exchange nothing.
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_sections_batch(OptArgs a, const float* __restrict__ terms,
+                                                                           float* __restrict__ rows, double lr, double beta1,
+                                                                           double beta2, float eps, int32_t* __restrict__ state,
+                                                                           int sections) {
+    const int item = blockIdx.x;
+    const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
+    auto term = [&](int k) { return mine[k]; };
+    opt_step<false, decltype(term), true>(a, item, term, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+                                          state + (int64_t)item * (kOptHdr + 2 * a.n_params), OptBest{}, sections);
+}
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_sections_batch(OptArgs a, const float* __restrict__ terms,
+                                                                                float* __restrict__ rows, double lr, double beta1,
+                                                                                double beta2, float eps, int32_t* __restrict__ state,
+                                                                                OptBest best, int sections) {
+    const int item = blockIdx.x;
+    const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
+    best.block += (int64_t)item * (kBestHdr + a.n_params + 1 + MST_OPT_MAX_TERMS);
+    auto term = [&](int k) { return mine[k]; };
+    opt_step<true, decltype(term), true>(a, item, term, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+                                         state + (int64_t)item * (kOptHdr + 2 * a.n_params), best, sections);
 }
 
 namespace {
@@ -431,5 +478,36 @@ extern "C" int mst_logit_adam_step_sections(const mst_logit_adam_segment* segmen
     else
         hipLaunchKernelGGL(k_logit_adam_step_sections, dim3(1), dim3(kOptWG), 0, (hipStream_t)stream, a, history_row, lr, beta1, beta2,
                            (float)eps, (int32_t*)state, (int)sections);
+    return (int)hipGetLastError();
+}
+
+// ---- several parameter sets, several gradient rows each: a batch of sectioned fits ------------------------------------------------
+extern "C" int mst_logit_adam_init_sections_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items,
+                                                  int32_t sections, void* state, void* stream) {
+    OptArgs a;
+    if (sections < 1 || sections > kOptMaxSections || !opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_logit_adam_init_sections_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, (int32_t*)state,
+                       (int)sections);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_logit_adam_step_sections_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items,
+                                                  int32_t sections, const float* loss_terms, int32_t n_terms, float* history_rows,
+                                                  double lr, double beta1, double beta2, double eps, double min_delta, int32_t patience,
+                                                  void* state, void* best, void* stream) {
+    OptArgs a;
+    OptBest b{};
+    if (sections < 1 || sections > kOptMaxSections || !opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3) ||
+        !history_rows || ((uintptr_t)history_rows & 3) || !loss_terms || ((uintptr_t)loss_terms & 3) || n_terms < 1 ||
+        n_terms > MST_OPT_MAX_TERMS)
+        return hipErrorInvalidValue;
+    if (!opt_hyper_ok(lr, beta1, beta2, eps) || (best && !opt_best(best, min_delta, patience, b))) return hipErrorInvalidValue;
+    a.n_terms = n_terms;
+    if (best)
+        hipLaunchKernelGGL(k_logit_adam_step_best_sections_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms,
+                           history_rows, lr, beta1, beta2, (float)eps, (int32_t*)state, b, (int)sections);
+    else
+        hipLaunchKernelGGL(k_logit_adam_step_sections_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms,
+                           history_rows, lr, beta1, beta2, (float)eps, (int32_t*)state, (int)sections);
     return (int)hipGetLastError();
 }

@@ -222,6 +222,9 @@ SIGNATURES = {
     "mst_logit_adam_init_sections": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, _P, _S]),
     "mst_logit_adam_step_sections": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _P,
                                               C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
+    "mst_logit_adam_init_sections_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.c_int32, _P, _S]),
+    "mst_logit_adam_step_sections_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                                    C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

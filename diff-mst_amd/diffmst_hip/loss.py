@@ -279,6 +279,15 @@ def _af_check_input(x, what):
         raise ValueError(f"AudioFeatureLoss expects a (bs, 2, seq_len) {what}, got {tuple(x.shape)}")
 
 
+def _af_check_items(items, rows, what):
+    """``items`` groups of consecutive rows: a positive whole number that divides the row count -> that number."""
+    if isinstance(items, bool) or int(items) != items or int(items) < 1:
+        raise ValueError(f"items must be a positive whole number, got {items!r}")
+    if rows % int(items):
+        raise ValueError(f"the {what} has {rows} rows, which items={items} does not divide (rows are item-major: items * sections)")
+    return int(items)
+
+
 class _AudioFeatureProfileFunction(torch.autograd.Function):
     """The loss of ``pred`` against a profile: the prediction's half of ``_AudioFeatureFunction``'s work."""
 
@@ -352,39 +361,41 @@ class _AudioFeatureItemsFunction(torch.autograd.Function):
 
 
 class _AudioFeaturePooledFunction(torch.autograd.Function):
-    """The loss of the rows of ``pred`` TAKEN TOGETHER against one profile row: five ``(1,)`` outputs, one cotangent row."""
+    """The loss of the rows of ``pred`` TAKEN TOGETHER, ``items`` groups of consecutive rows against a profile row each: five
+    ``(items,)`` outputs, a cotangent row per item."""
 
     @staticmethod
-    def forward(ctx, pred, profile, weights, sample_rate):
+    def forward(ctx, pred, profile, weights, sample_rate, items=1):
         lib = _hip.lib()
         x = pred.float().contiguous()
-        sections, _, n = x.shape
+        bs, _, n = x.shape
+        sections = bs // items
         dev = x.device
         tables, fb = _af_constants(dev, sample_rate)
-        nbytes = lib.mst_afloss_profile_workspace_bytes(sections, n)
+        nbytes = lib.mst_afloss_profile_workspace_bytes(bs, n)
         if nbytes == 0:
             raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        losses = torch.empty(1, 5, dtype=torch.float32, device=dev)
+        losses = torch.empty(items, 5, dtype=torch.float32, device=dev)
         w = (ctypes.c_float * 5)(*[float(v) for v in weights])
         with _hip.launch_on(dev) as st:
-            lib.mst_afloss_forward_profile_pooled(x, profile, 1, sections, n, w, tables, fb, losses, ws, nbytes, st)
-        ctx.meta = (sections, n, w, nbytes, pred.shape)
+            lib.mst_afloss_forward_profile_pooled(x, profile, items, sections, n, w, tables, fb, losses, ws, nbytes, st)
+        ctx.meta = (items, sections, n, w, nbytes, pred.shape)
         ctx.save_for_backward(x, profile, tables, fb, ws)
-        return tuple(losses.unbind(1))  # five (1,) views of one buffer
+        return tuple(losses.unbind(1))  # five (items,) views of one buffer
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grad_each):
         x, profile, tables, fb, ws = ctx.saved_tensors
-        sections, n, w, nbytes, shape = ctx.meta
+        items, sections, n, w, nbytes, shape = ctx.meta
         lib = _hip.lib()
         dev = x.device
-        g = torch.stack([gi.float().reshape(1) for gi in grad_each], dim=1).contiguous()  # (1, 5)
+        g = torch.stack([gi.float().reshape(items) for gi in grad_each], dim=1).contiguous()  # (items, 5)
         gx = torch.empty_like(x)
         with _hip.launch_on(dev) as st:
-            lib.mst_afloss_backward_profile_pooled(x, profile, 1, sections, n, w, tables, fb, g, gx, ws, nbytes, st)
-        return gx.view(shape), None, None, None
+            lib.mst_afloss_backward_profile_pooled(x, profile, items, sections, n, w, tables, fb, g, gx, ws, nbytes, st)
+        return gx.view(shape), None, None, None, None
 
 
 class AudioFeatureLoss(torch.nn.Module):
@@ -414,15 +425,20 @@ class AudioFeatureLoss(torch.nn.Module):
     Profile = AudioFeatureProfile  # reachable wherever this class is: ``mst.loss.AudioFeatureLoss.Profile`` after ``install()``
 
     @torch.no_grad()
-    def profile(self, x: torch.Tensor, pool: bool = False) -> AudioFeatureProfile:
+    def profile(self, x: torch.Tensor, pool: bool = False, items: int = 1) -> AudioFeatureProfile:
         """Analyse ``x (bs, 2, n)``, ``n > 16384``, on its device -> ``AudioFeatureProfile``.  No gradient reaches ``x``: the target
         side of this loss never receives one.
 
         ``pool=True``: the rows of ``x`` are sections of ONE signal and the result is one profile of batch size 1, pooled over them as
         ``pooled`` pools its input (``include/diffmst_hip.h``, ``mst_af_profile_pooled``): rms, crest factor, width and imbalance of the
-        concatenation, the mean magnitude spectrum over all frames of all sections.  For a reference given as sections."""
+        concatenation, the mean magnitude spectrum over all frames of all sections.  For a reference given as sections.  With
+        ``items=B`` as well, ``x`` is ``(B * R, 2, n)``, item-major, and the result has batch size ``B``: every item pooled over its
+        own ``R`` rows."""
         _hip.require_cuda(x)
         _af_check_input(x, "signal")
+        if not pool and items != 1:
+            raise ValueError("items needs pool=True: without pooling every row of x is a profile row of its own")
+        items = _af_check_items(items, x.shape[0], "signal")
         lib = _hip.lib()
         x = x.detach().float().contiguous()
         bs, _, n = x.shape
@@ -432,15 +448,15 @@ class AudioFeatureLoss(torch.nn.Module):
             raise ValueError("AudioFeatureLoss needs seq_len > 16384 (reflect padding of the 32768-point Bark STFT)")
         tables, fb = _af_constants(dev, self.sample_rate)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        data = torch.empty(1 if pool else bs, _cabi.AF_PROFILE_DOUBLES, dtype=torch.float64, device=dev)
+        data = torch.empty(items if pool else bs, _cabi.AF_PROFILE_DOUBLES, dtype=torch.float64, device=dev)
         with _hip.launch_on(dev) as st:
             if pool:
-                lib.mst_af_profile_pooled(x, 1, bs, n, tables, fb, data, ws, nbytes, st)
+                lib.mst_af_profile_pooled(x, items, bs // items, n, tables, fb, data, ws, nbytes, st)
             else:
                 lib.mst_af_profile(x, bs, n, tables, fb, data, ws, nbytes, st)
-        return AudioFeatureProfile(data, self.sample_rate, bs * n if pool else n)
+        return AudioFeatureProfile(data, self.sample_rate, bs // items * n if pool else n)
 
-    def pooled(self, input: torch.Tensor, target):
+    def pooled(self, input: torch.Tensor, target, items: int = 1):
         """The five terms of the rows of ``input (S, 2, n)`` TAKEN TOGETHER - S sections of one mix as one signal:
         ``{key: (1,) float32 device tensor}``, differentiable in ``input``.  All five features are aggregates over time, so the features
         of several sections are formed from the sections' sums, peaks and mean magnitudes before the nonlinear maps
@@ -449,7 +465,12 @@ class AudioFeatureLoss(torch.nn.Module):
         S crest factors is not the crest factor of the whole.  ``S = 1`` is ``per_item`` at batch 1, bit for bit.
 
         ``target`` is an ``AudioFeatureProfile`` of batch size 1 or a ``(1, 2, m)`` tensor of any length ``m > 16384``, which is
-        profiled on the way.  Errors as ``per_item``'s."""
+        profiled on the way.  Errors as ``per_item``'s.
+
+        ``items=B`` pools ``B`` groups at once: ``input`` is ``(B * S, 2, n)``, item-major (row ``b * S + s`` is section ``s`` of item
+        ``b``), the terms are ``(B,)`` tensors, a cotangent on element ``b`` reaches item ``b``'s rows only, and ``target`` is a profile
+        of batch size ``B`` or 1 (one reference for every item) or a ``(B, 2, m)`` tensor.  A row count that ``items`` does not divide
+        raises ``ValueError``.  For a batch of sectioned fits (``mst.online.optimize_sections_batch``)."""
         is_profile = isinstance(target, AudioFeatureProfile)
         if not is_profile and not isinstance(target, torch.Tensor):
             raise TypeError(f"AudioFeatureLoss takes a tensor or an AudioFeatureProfile as target, got {type(target).__name__}")
@@ -460,13 +481,17 @@ class AudioFeatureLoss(torch.nn.Module):
                 raise ValueError(f"the profile was taken at {target.sample_rate} Hz, this loss runs at {self.sample_rate} Hz")
         else:
             _af_check_input(target, "target")
+        items = _af_check_items(items, input.shape[0], "input")
         have = target.batch_size if is_profile else target.shape[0]
-        if have != 1:
-            raise ValueError(f"the sections of the input are pooled into one row, the target has batch size {have}")
+        if have != items and not (is_profile and have == 1):
+            if items == 1:
+                raise ValueError(f"the sections of the input are pooled into one row, the target has batch size {have}")
+            raise ValueError(f"the sections of the input are pooled into {items} rows, the target has batch size {have}")
         if not is_profile:
             target = self.profile(target)
         _hip.require_same_device(input.device, target.data)
-        losses = _AudioFeaturePooledFunction.apply(input, target.data, tuple(self.weights), self.sample_rate)
+        data = target.data if have == items else target.data.expand(items, -1).contiguous()
+        losses = _AudioFeaturePooledFunction.apply(input, data, tuple(self.weights), self.sample_rate, items)
         return dict(zip(AF_KEYS, losses))
 
     def per_item(self, input: torch.Tensor, target):

@@ -12,13 +12,18 @@ keeps the step count there.  The host reads nothing between the first and the la
 picks the best restart of a batch: ``mst_logit_adam_step_best`` / ``_step_best_batch`` keep the best logits in a second block on the
 device inside the same one launch.
 
+``optimize_sections`` fits ONE parameter set through several sections of a song pooled into one feature vector, and
+``optimize_sections_batch`` runs a batch of such fits - restarts, several references - in the launches of one.
+
 PARITY UNPINNED: the script cannot be imported (it imports ``StereoCLAPLoss``, which the reference's ``mst/loss.py`` does not define),
 so its loop is restated here and checked against ``torch.optim.Adam`` behind ``torch.sigmoid`` on recorded gradients.
 """
 from __future__ import annotations
 
 import ctypes
+import inspect
 import struct
+from collections.abc import Mapping
 from types import SimpleNamespace
 from typing import NamedTuple
 
@@ -84,7 +89,8 @@ def _segments(logits, params, grads):
 
 def _init(logits, params, items=None, sections=None):
     """p <- sigmoid(logits) by the kernel every later p comes from, and a zeroed optimiser state: one block, or with ``items`` one
-    block per item of the leading dimension.  With ``sections`` one block, and ``params`` has that many equal rows per logit row."""
+    block per item of the leading dimension.  With ``sections`` one block, and ``params`` has that many equal rows per logit row;
+    with both, one block per item and ``items * sections`` rows, item-major."""
     lib = _hip.lib()
     dev = logits[0].device
     total = sum(t.numel() for t in logits)
@@ -97,7 +103,9 @@ def _init(logits, params, items=None, sections=None):
         raise ValueError(f"more parameters per fit than the logit-Adam kernel takes (2^20), or more than {_cabi.OPT_MAX_ITEMS} fits")
     state = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     with _hip.launch_on(dev) as st:
-        if sections is not None:
+        if sections is not None and items is not None:
+            lib.mst_logit_adam_init_sections_batch(_segments(logits, params, none), len(logits), items, sections, state, st)
+        elif sections is not None:
             lib.mst_logit_adam_init_sections(_segments(logits, params, none), len(logits), sections, state, st)
         elif items is None:
             lib.mst_logit_adam_init(_segments(logits, params, none), len(logits), state, st)
@@ -170,9 +178,64 @@ def _check_sections(tracks, ref_mix, is_profile, loss_function):
     return S
 
 
+def _takes_items(pooled):
+    """Whether ``pooled`` can be called as ``pooled(input, target, items=B)``."""
+    try:
+        params = inspect.signature(pooled).parameters.values()
+    except (TypeError, ValueError):  # no signature to look at: the call itself will tell
+        return True
+    return any(p.kind is p.VAR_KEYWORD or (p.name == "items" and p.kind is not p.POSITIONAL_ONLY) for p in params)
+
+
+def _check_sections_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch):
+    """Types and shapes of ``optimize_sections_batch``, before anything touches the device -> (B, S, init scales)."""
+    pooled = getattr(loss_function, "pooled", None)
+    if not callable(pooled) or not _takes_items(pooled):
+        raise TypeError("optimize_sections_batch needs a loss_function with a pooled(input, target, items=B) method "
+                        f"(AudioFeatureLoss.pooled): {type(loss_function).__name__} has none")
+    if not isinstance(tracks, torch.Tensor) or tracks.dim() not in (3, 4):
+        raise ValueError("tracks must be (B, S, n_tracks, n_samples), or (S, n_tracks, n_samples) with batch=B")
+    if tracks.dim() == 4:
+        if batch is not None and int(batch) != tracks.shape[0]:
+            raise ValueError(f"batch={batch} with tracks of batch size {tracks.shape[0]}")
+        B = tracks.shape[0]
+    elif batch is None:
+        raise ValueError("tracks of shape (S, n_tracks, n_samples) need batch=B (the sectioned song is repeated B times)")
+    else:
+        B = int(batch)
+    S = tracks.shape[-3]
+    if not 1 <= B <= _cabi.OPT_MAX_ITEMS:
+        raise ValueError(f"the batch size must be 1..{_cabi.OPT_MAX_ITEMS}, got {B}")
+    if not 1 <= S <= _cabi.OPT_MAX_SECTIONS:
+        raise ValueError(f"the number of sections must be 1..{_cabi.OPT_MAX_SECTIONS}, got {S}")
+    if is_profile:
+        if ref_mix.batch_size not in (1, B):
+            raise ValueError(f"a profile given as ref_mix must have batch size {B} or 1, got {ref_mix.batch_size}")
+    elif not (ref_mix.dim() == 2 and ref_mix.shape[0] == 2) and not (ref_mix.dim() == 3 and tuple(ref_mix.shape[:2]) == (B, 2)) and not (
+            ref_mix.dim() == 4 and ref_mix.shape[0] == B and ref_mix.shape[1] >= 1 and ref_mix.shape[2] == 2):
+        raise ValueError(f"ref_mix must be (2, n_samples), ({B}, 2, n_samples), ({B}, R, 2, n_samples) - R sections of each item's "
+                         f"reference - or an AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+    if isinstance(init_scale, (int, float)):
+        scales = [float(init_scale)] * B
+    else:
+        scales = [float(v) for v in init_scale]
+        if len(scales) != B:
+            raise ValueError(f"init_scale must be a number or a sequence of {B} numbers, got {len(scales)}")
+    _hip.require_cuda(tracks, ref_mix.data if is_profile else ref_mix)
+    return B, S, scales
+
+
+def _first_sections(value, B, S):
+    """Section 0 of every item of what a console at batch ``B * S`` returned: rows ``b * S`` of every tensor, through dictionaries."""
+    if isinstance(value, Mapping):  # a console built with param_dicts="lazy" fills its dictionaries here, after the loop
+        return {k: _first_sections(v, B, S) for k, v in value.items()}
+    return value[::S] if isinstance(value, torch.Tensor) and value.dim() >= 1 and value.shape[0] == B * S else value
+
+
 class _Run:
     """One optimisation, or with ``batch`` a batch of independent ones in the same launches: set-up (the start point goes to the
-    device), ``iterate(n)`` (nothing in it waits for the device) and ``finish()`` (the one read of history and status)."""
+    device), ``iterate(n)`` (nothing in it waits for the device) and ``finish()`` (the one read of history and status).  ``sectioned``
+    gives every parameter set ``S`` sections; with ``batched`` as well, ``items`` and ``sections`` are both set."""
 
     def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
                  batch=None, batched=False, keep_best=False, patience=None, min_delta=0.0, poll_every=None, sectioned=False):
@@ -182,7 +245,10 @@ class _Run:
         if not is_profile and not isinstance(ref_mix, torch.Tensor):
             raise TypeError(f"ref_mix must be a (2, n_samples) tensor or an AudioFeatureProfile, got {type(ref_mix).__name__}")
         self.sections = None  # S: one parameter set fitted to S sections in the launches of one (optimize_sections)
-        if sectioned:
+        self.name = "optimize_sections_batch" if sectioned and batched else "optimize_batch" if batched else "optimize"
+        if sectioned and batched:
+            self.items, self.sections, scales = _check_sections_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch)
+        elif sectioned:
             self.items, self.sections = None, _check_sections(tracks, ref_mix, is_profile, loss_function)
         elif batched:
             self.items, scales = _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch)
@@ -197,7 +263,10 @@ class _Run:
         self.flags = dict(use_fx_bus=False)
         self.flags.update(console_flags)
         n_tracks, n_samples = tracks.shape[-2:]
-        if self.sections is not None:
+        if self.sections is not None and B is not None:  # (B * S, T, n), item-major: row b * S + s is section s of item b
+            rows = tracks.detach() if tracks.dim() == 4 else tracks.detach().unsqueeze(0).repeat(B, 1, 1, 1)
+            self.tracks = rows.reshape(B * self.sections, n_tracks, n_samples).contiguous()
+        elif self.sections is not None:
             self.tracks = tracks.detach()
         elif B is None:
             self.tracks = tracks.detach().unsqueeze(0)
@@ -205,6 +274,13 @@ class _Run:
             self.tracks = tracks.detach() if tracks.dim() == 3 else tracks.detach().unsqueeze(0).repeat(B, 1, 1)
         if is_profile:
             self.ref_mix = ref_mix
+        elif self.sections is not None and B is not None:
+            # analysed here, once: one reference for every item, one per item, or one per item given as R sections and pooled
+            ref = ref_mix.detach()
+            if ref.dim() == 4:
+                self.ref_mix = loss_function.profile(ref.reshape((-1,) + tuple(ref.shape[2:])), pool=True, items=B)
+            else:
+                self.ref_mix = loss_function.profile(ref.unsqueeze(0) if ref.dim() == 2 else ref)
         elif self.sections is not None:
             # the pooled loss has no paired route: the reference is analysed here, once - its sections pooled if it comes as sections
             ref = ref_mix.detach()
@@ -233,8 +309,9 @@ class _Run:
                                 for i in range(3))
         if self.sections is None:
             self.params = tuple(torch.empty_like(t).requires_grad_(True) for t in self.logits)  # leaves the kernel rewrites
-        else:  # (S, T, 27), (S, 25), (S, 26) leaves whose rows the kernel keeps equal: the console runs at batch S
-            self.params = tuple(torch.empty((self.sections,) + t.shape[1:], dtype=t.dtype, device=dev).requires_grad_(True)
+        else:  # (S, T, 27), (S, 25), (S, 26) leaves whose rows the kernel keeps equal: the console runs at batch S - or, for a batch
+            # of sectioned fits, (B S, ...) leaves whose rows are equal within an item: the console runs at batch B S
+            self.params = tuple(torch.empty(((B or 1) * self.sections,) + t.shape[1:], dtype=t.dtype, device=dev).requires_grad_(True)
                                 for t in self.logits)
         self.state = _init(self.logits, self.params, B, self.sections)
         self.best = None
@@ -248,7 +325,9 @@ class _Run:
         lib = _hip.lib()
         B = self.items
         self.result = result = self.console(self.tracks, *self.params, **self.flags)
-        if self.sections is not None:
+        if self.sections is not None and B is not None:
+            losses = self.loss_function.pooled(result[1], self.ref_mix, items=B)
+        elif self.sections is not None:
             losses = self.loss_function.pooled(result[1], self.ref_mix)
         else:
             losses = (self.loss_function if B is None else self.loss_function.per_item)(result[1], self.ref_mix)
@@ -287,7 +366,10 @@ class _Run:
         else:
             dense = torch.stack([t.detach() for t in terms], dim=1)  # (B, n_terms), after the callback: it sees what the callback left
             with _hip.launch_on(self.tracks.device) as st:
-                if self.keep_best:
+                if self.sections is not None:  # every item's S gradient rows are summed inside the step
+                    lib.mst_logit_adam_step_sections_batch(segments, len(self.logits), B, self.sections, dense, len(terms), row,
+                                                           *self.hyper, self.min_delta, self.patience, self.state, self.best, st)
+                elif self.keep_best:
                     lib.mst_logit_adam_step_best_batch(segments, len(self.logits), B, dense, len(terms), row, *self.hyper,
                                                        self.min_delta, self.patience, self.state, self.best, st)
                 else:
@@ -310,6 +392,12 @@ class _Run:
         stopped = self.state.view(B, -1)[:, 1]
         return bool(((settled != 0) | (stopped != 0)).all())
 
+    def _per_item(self, mix, *dicts):
+        """What a console at batch ``B S`` returned, as a batch of sectioned fits returns it: ``mix (B, S, 2, n)`` and the
+        dictionaries at batch ``B`` (section 0 of every item: all rows of an item are equal)."""
+        B, S = self.items, self.sections
+        return (mix.reshape((B, S) + tuple(mix.shape[1:])),) + tuple(_first_sections(d, B, S) for d in dicts)
+
     def _finish_best(self):
         """The best iterate in place of the last one: its logits out of the best block, its parameters by the init launch (the sigmoid
         bits the loop used), one console forward under ``no_grad`` -> (mix, logits, dictionaries, report columns, state words)."""
@@ -322,7 +410,7 @@ class _Run:
         has_best = [w[0] != 0 for w in words]
         if not any(has_best):
             where = [w[2] for w in state_words]
-            raise FloatingPointError(f"{'optimize_batch' if self.items else 'optimize'}: no iteration had a finite loss and gradient "
+            raise FloatingPointError(f"{self.name}: no iteration had a finite loss and gradient "
                                      f"(first at iteration{'s' if self.items else ''} {where if self.items else where[0]}); the "
                                      "parameters were left as they stood")
         stored = block[:, hdr:hdr + sum(counts)].view(torch.float32).split(counts, dim=1)
@@ -331,10 +419,12 @@ class _Run:
         logits = tuple(torch.where(keep.view((B,) + (1,) * (live.dim() - 1)), got.reshape(live.shape), live).contiguous()
                        for got, live in zip(stored, self.logits))
         with torch.no_grad():
-            rows = (lambda t: t.shape) if self.sections is None else (lambda t: (self.sections,) + t.shape[1:])
+            rows = (lambda t: t.shape) if self.sections is None else (lambda t: (B * self.sections,) + t.shape[1:])
             params = tuple(torch.empty(rows(t), dtype=t.dtype, device=t.device) for t in logits)
             _init(logits, params, self.items, self.sections)
             _, mix, track_dict, fx_dict, master_dict = self.console(self.tracks, *params, **self.flags)
+            if self.items is not None and self.sections is not None:
+                mix, track_dict, fx_dict, master_dict = self._per_item(mix, track_dict, fx_dict, master_dict)
         best_loss = [struct.unpack("f", struct.pack("i", w[1]))[0] if ok else float("inf") for w, ok in zip(words, has_best)]
         report = FitReport([w[0] - 1 if ok else None for w, ok in zip(words, has_best)], best_loss,
                            [w[3] - 1 if w[3] else None for w in words], [self.ran] * B)
@@ -360,9 +450,11 @@ class _Run:
             words = self.state.view(self.items, -1)[:, :4].tolist()
             stopped_at = [where if status else None for _, status, where, _ in words]
             if all(w is not None for w in stopped_at):
-                raise FloatingPointError(f"optimize_batch: every item met a loss term or a gradient that was not finite (first at "
+                raise FloatingPointError(f"{self.name}: every item met a loss term or a gradient that was not finite (first at "
                                          f"iterations {stopped_at}); those iterations left the parameters as they stood")
             loss_history = {name: history[:, :, i].clone() for i, name in enumerate(names)}
+            if self.sections is not None:
+                mix, track_dict, fx_dict, master_dict = self._per_item(mix, track_dict, fx_dict, master_dict)
             return mix.detach(), lt, track_dict, lf, fx_dict, lm, master_dict, loss_history, stopped_at
         t, status, where, _ = self.state[:4].tolist()
         if self.sections is not None:
@@ -492,6 +584,35 @@ def optimize_sections(tracks, ref_mix, mix_console, loss_function, init_scale=0.
     ``(1, T, 27)``, ``(1, 25)``, ``(1, 26)``, ready for ``render_blocks``.  ``S = 1`` against a profile is ``optimize`` bit for bit."""
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
                keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every, sectioned=True)
+    return run.loop()
+
+
+def optimize_sections_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, batch=None,
+                            betas=(0.9, 0.999), eps=1e-8, generator=None, callback=None, keep_best=False, patience=None,
+                            min_delta=0.0, poll_every=None, **console_flags):
+    """``B`` independent ``optimize_sections`` fits in the launches of one: restarts of a sectioned fit (``best_of`` keeps
+    the best), one sectioned song against several references.  Per iteration one console forward at batch ``B S`` with parameter leaves
+    ``(B S, T, 27)``, ``(B S, 25)``, ``(B S, 26)`` whose rows are equal within an item, ``loss_function.pooled(mix, target, items=B)``,
+    one ``torch.autograd.grad`` with a ones cotangent per ``(B,)`` term and ONE ``mst_logit_adam_step_sections_batch``, which sums every
+    item's ``S`` gradient rows in section order; nothing in the loop waits for the host.
+
+    ``tracks`` is ``(B, S, T, n)``, or ``(S, T, n)`` with ``batch=B`` (the sectioned song is repeated: restarts).  Rows are item-major:
+    the console sees row ``b S + s`` for section ``s`` of item ``b``.  ``ref_mix`` is ``(2, M)`` (one reference for every item),
+    ``(B, 2, M)``, ``(B, R, 2, M)`` - every item's reference as ``R`` sections, pooled - or an ``AudioFeatureProfile`` of batch size ``B``
+    or 1; a tensor is analysed once, before the loop.  ``loss_function`` must offer ``pooled`` with ``items`` (``AudioFeatureLoss``):
+    anything else raises ``TypeError``.  ``init_scale`` is a number or ``B`` numbers; item ``b`` starts at the ``b``-th successive
+    ``start_point()`` draw, as in ``optimize_batch``, so ``B = 1`` is ``optimize_sections`` and ``S = 1`` is ``optimize_batch`` against a
+    profile, both bit for bit.
+
+    Returns ``optimize_batch``'s 9-tuple (10 with ``keep_best``: the ``FitReport`` of lists): ``mix (B, S, 2, n)``, logits
+    ``(B, T, 27)``, ``(B, 25)``, ``(B, 26)``, the dictionaries at batch ``B`` (section 0 of every item), ``loss_history[name]`` an
+    ``(n_iters, B)`` host tensor and ``stopped_at``.  ``keep_best``, ``patience``, ``min_delta`` and ``poll_every`` work per item, a
+    non-finite item stops alone, and ``FloatingPointError`` is raised only when every item stopped (with ``keep_best``: when no item has
+    a best iterate).  ``pick(result, b)`` is item ``b`` as ``optimize_sections`` returns it - ``mix (S, 2, n)``, logits ready for
+    ``render_blocks`` - and ``best_of(result)`` the item with the lowest best loss."""
+    run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
+               batch=batch, batched=True, keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every,
+               sectioned=True)
     return run.loop()
 
 

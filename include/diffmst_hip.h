@@ -426,6 +426,26 @@ int mst_logit_adam_step_sections(const mst_logit_adam_segment* segments, int32_t
                                  const float* const* loss_terms, int32_t n_terms, float* history_row, double lr, double beta1, double beta2,
                                  double eps, double min_delta, int32_t patience, void* state, void* best, void* stream);
 
+/* A BATCH of sectioned fits: `items` parameter sets with `sections` gradient rows each, in ONE launch of `items`
+ * workgroups - restarts of a sectioned fit, one sectioned song against several references.  Workgroup b is
+ * mst_logit_adam_step_sections on item b, the same operations in the same order, and exchanges nothing with the others.  Per segment
+ *   theta           `count` = items * c elements, item-major, as in the batch calls: item b owns [b c, (b + 1) c)
+ *   p, grad_p       dense (items, sections, c): row item * sections + r is section r of `item` - the item-major order of the pooled
+ *                   loss calls below and of a console that runs at batch items * sections
+ *   state, best     mst_logit_adam_batch_state_bytes(items, sum of c), mst_logit_adam_best_bytes(items, sum of c): the batch layouts
+ *   loss_terms      device, dense (items, n_terms) fp32;  history_rows  device, dense (items, 1 + n_terms) fp32
+ * Item b's gradient at a coordinate is ((g_0 + g_1) + g_2) + ... over ITS rows in fp32; p is read from its row 0 and the new p goes
+ * to all of its rows.  A non-finite addend, partial sum or loss term of item b stops item b's iteration alone.  `best` NULL: the plain
+ * step; non-NULL: the best-iterate step per item, as in mst_logit_adam_step_best_batch.  items = 1 gives the bits of the _sections
+ * calls, sections = 1 those of the _batch calls, in every output.  items outside [1, 1024], sections outside [1, 64], a count that
+ * `items` does not divide and every bad argument of those calls return non-zero before anything is launched. */
+int mst_logit_adam_init_sections_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, int32_t sections,
+                                       void* state, void* stream);
+int mst_logit_adam_step_sections_batch(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, int32_t sections,
+                                       const float* loss_terms, int32_t n_terms, float* history_rows, double lr, double beta1,
+                                       double beta2, double eps, double min_delta, int32_t patience, void* state, void* best,
+                                       void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
