@@ -147,6 +147,11 @@ static int console_forward_impl(const mst_console_desc* d, const float* tracks, 
         mirror_status(status, status_host, status_event, stream);
         return (int)hipGetLastError();
     }
+    // The backward's coefficient-gradient walk reads the all-pole chunk start states over the PADDED chunk count and multiplies the
+    // padding by samples that are exactly zero; no launch writes that padding and the workspace comes as the caller allocated it, so
+    // a NaN left there would come out as a NaN gradient.  Only lengths whose chunk count is no multiple of 256 have any.
+    if (save && L.ncE_pad != L.ncE)
+        (void)hipMemsetAsync(ws + L.sP_t, 0, (size_t)(L.R + 2 * L.bs) * 24 * L.ncE_pad * sizeof(float), stream);
 
     // ---- prep: row constants, scan tables and zero-state maps of every EQ pass of the call (both directions), granules zeroed
     EqPass eq_t = eq_rows(L, ws, EQ_TRACKS, EQ_FWD), eq_m = eq_rows(L, ws, EQ_MASTER, EQ_FWD);

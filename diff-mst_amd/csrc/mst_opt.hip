@@ -80,6 +80,30 @@ __device__ __forceinline__ float opt_section_sum(const float* __restrict__ dp, i
     }
     return sum;
 }
+// Linked rows: the gradient of the logit that the group led by row l shares at column c, ((g_m0 + g_m1) + ...) in fp32
+// over the members m in ascending order, the leader first.  g_m is the member's own chain through the sigmoid, its d_m the section sum
+// over ITS rows and p_m read from its own row 0, negated for a follower at the mirrored column (its logit is minus the leader's).
+// `bad` collects an addend or a partial sum that is not finite.  A row that leads itself alone: today's g, no addition.
+__device__ __forceinline__ float opt_group_sum(const float* __restrict__ dp, const float* __restrict__ p, int l, int c, int n, int sections,
+                                               const mst_logit_adam_links& k, const uint8_t* __restrict__ leader, bool& bad) {
+    float sum = 0.0f;
+    for (int m = l; m < k.rows; ++m) {
+        if (leader[m] != l) continue;
+        const int j = m * k.cols + c;
+        const float pm = p[j];
+        const float d = opt_section_sum(dp, j, n, sections, bad);
+        float g = (d * (1.0f - pm)) * pm;
+        if (m != l && c == k.mirror_col) g = -g;
+        bad |= !opt_finite(g);
+        if (m == l) {
+            sum = g;
+        } else {
+            sum = sum + g;
+            bad |= !opt_finite(sum);
+        }
+    }
+    return sum;
+}
 __global__ __launch_bounds__(kOptWG) void k_logit_adam_init(OptArgs a, int32_t* __restrict__ state) { opt_init(a, 0, state); }
 // ... for one parameter set whose p has `sections` equal rows: the init of the single kernel, its p written to every row
 __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_sections(OptArgs a, int32_t* __restrict__ state, int sections) {
@@ -122,6 +146,37 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_sections_batch(OptAr
         }
     }
 }
+// ... with linked rows in segment `links.segment`: a follower row takes its leader's logits, minus them at the mirrored
+// column, before the sigmoid; the lane of a follower coordinate reads the leader's logit, which no lane writes
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_init_linked(OptArgs a, int32_t* __restrict__ state, int sections,
+                                                                   mst_logit_adam_links links) {
+    const int tid = threadIdx.x;
+    const int item = blockIdx.x;
+    const int words = kOptHdr + 2 * a.n_params;
+    state += (int64_t)item * words;
+    for (int w = tid; w < words; w += kOptWG) state[w] = 0;
+#pragma unroll
+    for (int s = 0; s < MST_OPT_MAX_SEGMENTS; ++s) {
+        if (s >= a.n_segments) break;
+        const int n = a.count[s];
+        float* th = a.theta[s] + (int64_t)item * n;
+        float* __restrict__ p = a.p[s] + (int64_t)item * sections * n;
+        for (int i = tid; i < n; i += kOptWG) {
+            float ti = th[i];
+            if (s == links.segment) {
+                const int row = i / links.cols, c = i - row * links.cols;
+                const int l = links.leader[row];
+                if (l != row) {
+                    ti = th[l * links.cols + c];
+                    if (c == links.mirror_col) ti = -ti;
+                    th[i] = ti;
+                }
+            }
+            const float pi = opt_sigmoid(ti);
+            for (int r = 0; r < sections; ++r) p[(int64_t)r * n + i] = pi;
+        }
+    }
+}
 
 // One workgroup's whole step over its item's slices: the body of the four kernels below.  term(k) is loss term k of this item, `row`
 // its history row, `state` its block (header, first moments, second moments).  kBest adds the best-iterate bookkeeping on `best`;
@@ -130,10 +185,16 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_init_sections_batch(OptAr
 // coordinate is the sum of its rows (opt_section_sum) and the new p goes to every row.  Everything else is the same statements.
 // With kSections an item's rows of p and grad_p begin item * sections * count in (mst_logit_adam_step_sections_batch); the single
 // kernels run it with item = 0, where that is no offset at all.
-template <bool kBest, class Term, bool kSections = false>
+// kLinked (mst_logit_adam_step_linked; with kSections): in segment links->segment the rows of a group share one logit per
+// column.  Only the lane of a leader coordinate acts: the gradient is opt_group_sum over the members, the Adam statements run on the
+// leader's moments and logit, and theta, p and the snapshot are written for every member (minus the logit at the mirrored column of a
+// follower).  Lanes of follower coordinates write nothing, so their moment words stay zero.  `leader` is the map in LDS, written by
+// the kernel before the call; the first barrier below publishes it.  The other instantiations have none of this code.
+template <bool kBest, class Term, bool kSections = false, bool kLinked = false>
 __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, float* __restrict__ row, double lr, double beta1,
                                          double beta2, float eps, int32_t* __restrict__ state, OptBest best = OptBest{},
-                                         int sections = 1) {
+                                         int sections = 1, const mst_logit_adam_links* links = nullptr,
+                                         const uint8_t* __restrict__ leader = nullptr) {
     __shared__ int s_bad;
     __shared__ int s_best;
     __shared__ float s_step, s_c2;
@@ -156,6 +217,16 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
         if (!a.grad_p[s]) continue;
         // an item's rows of grad_p (and of p below) lie item * sections * count in; its theta item * count
         const float* __restrict__ dp = a.grad_p[s] + (kSections ? (int64_t)item * sections * a.count[s] : (int64_t)item * a.count[s]);
+        if constexpr (kLinked) {
+            if (s == links->segment) {  // every row is a member of one group: its leader's lane looks at it
+                const float* __restrict__ p = a.p[s] + (int64_t)item * sections * a.count[s];
+                for (int i = tid; i < a.count[s]; i += kOptWG) {
+                    const int l = i / links->cols;
+                    if (leader[l] == l) opt_group_sum(dp, p, l, i - l * links->cols, a.count[s], sections, *links, leader, bad);
+                }
+                continue;
+            }
+        }
         if (kSections) {
             for (int i = tid; i < a.count[s]; i += kOptWG) opt_section_sum(dp, i, a.count[s], sections, bad);
         } else {
@@ -225,6 +296,33 @@ __device__ __forceinline__ void opt_step(const OptArgs& a, int item, Term term, 
             float* __restrict__ p = a.p[s] + rows;
             float* __restrict__ m = m_all + at;
             float* __restrict__ v = v_all + at;
+            if constexpr (kLinked) {
+                if (s == links->segment) {
+                    const int cols = links->cols;
+                    for (int i = tid; i < n; i += kOptWG) {
+                        const int l = i / cols, c = i - l * cols;
+                        if (leader[l] != l) continue;
+                        bool ignored = false;
+                        const float g = opt_group_sum(dp, p, l, c, n, sections, *links, leader, ignored);
+                        const float mi = m[i] + w1 * (g - m[i]);
+                        const float vi = v[i] * b2 + (w2 * g) * g;
+                        const float ti = th[i] + (step * mi) / (sqrtf(vi) / c2 + eps);
+                        m[i] = mi;
+                        v[i] = vi;
+                        for (int f = l; f < links->rows; ++f) {  // the members, the leader first: this lane alone touches them
+                            if (leader[f] != l) continue;
+                            const int j = f * cols + c;
+                            if (improved) snap[at + j] = th[j];  // the member's own logit the loss was evaluated at
+                            const float tj = (f != l && c == links->mirror_col) ? -ti : ti;
+                            th[j] = tj;
+                            const float pn = opt_sigmoid(tj);
+                            for (int r = 0; r < sections; ++r) p[(int64_t)r * n + j] = pn;
+                        }
+                    }
+                    at += n;
+                    continue;
+                }
+            }
             for (int i = tid; i < n; i += kOptWG) {
                 const float pi = p[i];  // with sections: row 0, every row holds the same bits
                 bool ignored = false;
@@ -315,6 +413,34 @@ __global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_sections_batch(
     opt_step<true, decltype(term), true>(a, item, term, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
                                          state + (int64_t)item * (kOptHdr + 2 * a.n_params), best, sections);
 }
+// The two kernels above with linked rows (include/diffmst_hip.h).  The map is a kernel argument of its own, after every
+// argument of the kernels above; lane r copies leader[r] to LDS (MST_OPT_MAX_LINK_ROWS == the workgroup size) and the step's first
+// barrier publishes it.
+static_assert(MST_OPT_MAX_LINK_ROWS == kOptWG, "one lane per entry of the leader map");
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_linked(OptArgs a, const float* __restrict__ terms, float* __restrict__ rows,
+                                                                   double lr, double beta1, double beta2, float eps,
+                                                                   int32_t* __restrict__ state, int sections, mst_logit_adam_links links) {
+    __shared__ uint8_t s_leader[MST_OPT_MAX_LINK_ROWS];
+    s_leader[threadIdx.x] = links.leader[threadIdx.x];
+    const int item = blockIdx.x;
+    const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
+    auto term = [&](int k) { return mine[k]; };
+    opt_step<false, decltype(term), true, true>(a, item, term, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+                                                state + (int64_t)item * (kOptHdr + 2 * a.n_params), OptBest{}, sections, &links, s_leader);
+}
+__global__ __launch_bounds__(kOptWG) void k_logit_adam_step_best_linked(OptArgs a, const float* __restrict__ terms,
+                                                                        float* __restrict__ rows, double lr, double beta1, double beta2,
+                                                                        float eps, int32_t* __restrict__ state, OptBest best, int sections,
+                                                                        mst_logit_adam_links links) {
+    __shared__ uint8_t s_leader[MST_OPT_MAX_LINK_ROWS];
+    s_leader[threadIdx.x] = links.leader[threadIdx.x];
+    const int item = blockIdx.x;
+    const float* __restrict__ mine = terms + (int64_t)item * a.n_terms;
+    best.block += (int64_t)item * (kBestHdr + a.n_params + 1 + MST_OPT_MAX_TERMS);
+    auto term = [&](int k) { return mine[k]; };
+    opt_step<true, decltype(term), true, true>(a, item, term, rows + (int64_t)item * (1 + a.n_terms), lr, beta1, beta2, eps,
+                                               state + (int64_t)item * (kOptHdr + 2 * a.n_params), best, sections, &links, s_leader);
+}
 
 namespace {
 // the segment table as kernel arguments; false for what the kernels do not support
@@ -344,6 +470,18 @@ bool opt_best(void* best, double min_delta, int32_t patience, OptBest& b) {
     if (!best || ((uintptr_t)best & 3) || !(min_delta >= 0.0) || !isfinite(min_delta) || !isfinite((float)min_delta) || patience < 0)
         return false;
     b = OptBest{(int32_t*)best, (float)min_delta, patience};
+    return true;
+}
+// the link description of the `_linked` launchers against the segment table; false for what they refuse
+bool opt_links(const mst_logit_adam_links* links, const OptArgs& a) {
+    if (!links || links->segment < 0 || links->segment >= a.n_segments || links->rows < 1 || links->rows > MST_OPT_MAX_LINK_ROWS ||
+        links->cols < 1 || (int64_t)links->rows * links->cols != a.count[links->segment] || links->mirror_col < -1 ||
+        links->mirror_col >= links->cols)
+        return false;
+    for (int r = 0; r < links->rows; ++r) {
+        const int l = links->leader[r];
+        if (l > r || links->leader[l] != l) return false;
+    }
     return true;
 }
 }  // namespace
@@ -509,5 +647,37 @@ extern "C" int mst_logit_adam_step_sections_batch(const mst_logit_adam_segment* 
     else
         hipLaunchKernelGGL(k_logit_adam_step_sections_batch, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms,
                            history_rows, lr, beta1, beta2, (float)eps, (int32_t*)state, (int)sections);
+    return (int)hipGetLastError();
+}
+
+// ---- the same, with rows of one segment linked: tied logits and a mirrored column (stereo pairs) -----------------------------------
+extern "C" int mst_logit_adam_init_linked(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, int32_t sections,
+                                          const mst_logit_adam_links* links, void* state, void* stream) {
+    OptArgs a;
+    if (sections < 1 || sections > kOptMaxSections || !opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3) ||
+        !opt_links(links, a))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_logit_adam_init_linked, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, (int32_t*)state, (int)sections,
+                       *links);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_logit_adam_step_linked(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, int32_t sections,
+                                          const mst_logit_adam_links* links, const float* loss_terms, int32_t n_terms,
+                                          float* history_rows, double lr, double beta1, double beta2, double eps, double min_delta,
+                                          int32_t patience, void* state, void* best, void* stream) {
+    OptArgs a;
+    OptBest b{};
+    if (sections < 1 || sections > kOptMaxSections || !opt_args(segments, n_segments, a, items) || !state || ((uintptr_t)state & 3) ||
+        !history_rows || ((uintptr_t)history_rows & 3) || !loss_terms || ((uintptr_t)loss_terms & 3) || n_terms < 1 ||
+        n_terms > MST_OPT_MAX_TERMS || !opt_links(links, a))
+        return hipErrorInvalidValue;
+    if (!opt_hyper_ok(lr, beta1, beta2, eps) || (best && !opt_best(best, min_delta, patience, b))) return hipErrorInvalidValue;
+    a.n_terms = n_terms;
+    if (best)
+        hipLaunchKernelGGL(k_logit_adam_step_best_linked, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms, history_rows,
+                           lr, beta1, beta2, (float)eps, (int32_t*)state, b, (int)sections, *links);
+    else
+        hipLaunchKernelGGL(k_logit_adam_step_linked, dim3(items), dim3(kOptWG), 0, (hipStream_t)stream, a, loss_terms, history_rows, lr,
+                           beta1, beta2, (float)eps, (int32_t*)state, (int)sections, *links);
     return (int)hipGetLastError();
 }

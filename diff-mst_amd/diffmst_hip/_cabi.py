@@ -121,6 +121,7 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
 OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
 OPT_MAX_ITEMS = 1024  # items of mst_logit_adam_step_batch
 OPT_MAX_SECTIONS = 64  # sections of mst_logit_adam_step_sections
+OPT_MAX_LINK_ROWS = 256  # MST_OPT_MAX_LINK_ROWS: rows of the tied segment of mst_logit_adam_step_linked
 OPT_HEADER_WORDS = 16  # int32 words in front of an item's moments
 OPT_BEST_HEADER_WORDS = 16  # int32 words in front of an item's best logits (mst_logit_adam_step_best)
 AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
@@ -128,6 +129,11 @@ AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
 
 class LogitAdamSegment(C.Structure):  # mirrors mst_logit_adam_segment
     _fields_ = [("theta", C.c_void_p), ("p", C.c_void_p), ("grad_p", C.c_void_p), ("count", C.c_int64)]
+
+
+class LogitAdamLinks(C.Structure):  # mirrors mst_logit_adam_links
+    _fields_ = [("segment", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("mirror_col", C.c_int32),
+                ("leader", C.c_uint8 * OPT_MAX_LINK_ROWS)]
 
 
 def ptr(t):
@@ -225,6 +231,11 @@ SIGNATURES = {
     "mst_logit_adam_init_sections_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.c_int32, _P, _S]),
     "mst_logit_adam_step_sections_batch": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P,
                                                     C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _S]),
+    "mst_logit_adam_init_linked": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.c_int32, C.POINTER(LogitAdamLinks), _P,
+                                            _S]),
+    "mst_logit_adam_step_linked": (STATUS, [C.POINTER(LogitAdamSegment), C.c_int32, C.c_int32, C.c_int32, C.POINTER(LogitAdamLinks), _P,
+                                            C.c_int32, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P,
+                                            _S]),
     "mst_afloss_tables_bytes": (C.c_size_t, []),
     "mst_afloss_init_tables": (STATUS, [_P, _S]),
     "mst_afloss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),

@@ -15,6 +15,8 @@ device inside the same one launch.
 ``optimize_sections`` fits ONE parameter set through several sections of a song pooled into one feature vector, and
 ``optimize_sections_batch`` runs a batch of such fits - restarts, several references - in the launches of one.
 
+``links`` / ``stereo_id`` on all four tie the two mono rows of a stereo stem to one set of logits with a mirrored pan.
+
 PARITY UNPINNED: the script cannot be imported (it imports ``StereoCLAPLoss``, which the reference's ``mst/loss.py`` does not define),
 so its loop is restated here and checked against ``torch.optim.Adam`` behind ``torch.sigmoid`` on recorded gradients.
 """
@@ -29,7 +31,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _cabi, _hip
+from . import _cabi, _desc, _hip
 from .loss import AudioFeatureProfile
 
 
@@ -79,6 +81,67 @@ def start_point(n_tracks: int, mix_console, init_scale: float = 0.001, generator
     return tuple(init_scale * torch.randn(shape, generator=generator) for shape in shapes)
 
 
+def links_from_stereo_id(stereo_id):
+    """The reference's ``stereo_info`` flags -> the leader list ``optimize(..., links=...)`` takes.  ``stereo_id`` is a length-``T``
+    sequence or 1-D tensor; a non-zero entry at row ``t`` says that row ``t + 1`` is the other channel of the same stem (the loaders
+    split a stereo stem into two mono rows: reference scripts/online.py:229-240, mst/dataloader.py:321-336).  Row ``t + 1`` then
+    follows row ``t``; it is skipped when the flags are walked, as mst/mixing.py:268-722 skips it, and a flag on the last row has no
+    partner and is ignored (mst/mixing.py:280-283).  -> ``leader[r]``: the row whose settings row ``r`` shares, ``r`` itself if none."""
+    flags = stereo_id.tolist() if isinstance(stereo_id, torch.Tensor) else list(stereo_id)
+    if isinstance(stereo_id, torch.Tensor) and stereo_id.dim() != 1:
+        raise ValueError(f"stereo_id must be a sequence or a 1-D tensor of flags, got shape {tuple(stereo_id.shape)}")
+    leader, t = list(range(len(flags))), 0
+    while t < len(flags):
+        if flags[t] and t + 1 < len(flags):
+            leader[t + 1] = t
+            t += 2
+        else:
+            t += 1
+    return leader
+
+
+def _check_links(links, stereo_id, mirror_pan, tracks, mix_console):
+    """The three keywords of a linked fit, before anything touches the device -> None without links, else the C ABI's description of
+    the track segment: (rows, cols, mirror_col, leader list)."""
+    if links is None and stereo_id is None:
+        return None
+    if links is not None and stereo_id is not None:
+        raise ValueError("give links or stereo_id, not both")
+    if not isinstance(tracks, torch.Tensor) or tracks.dim() < 2:
+        raise ValueError("links need tracks of shape (..., n_tracks, n_samples)")
+    n_tracks = tracks.shape[-2]
+    if stereo_id is not None:
+        links = links_from_stereo_id(stereo_id)
+        what = "stereo_id"
+    else:
+        links = links.tolist() if isinstance(links, torch.Tensor) else list(links)
+        what = "links"
+    if len(links) != n_tracks:
+        raise ValueError(f"{what} must have one entry per track ({n_tracks}), got {len(links)}")
+    if n_tracks > _cabi.OPT_MAX_LINK_ROWS:
+        raise ValueError(f"a linked fit takes at most {_cabi.OPT_MAX_LINK_ROWS} tracks, got {n_tracks}")
+    for r, l in enumerate(links):
+        if int(l) != l or not 0 <= l <= r or links[int(l)] != l:
+            raise ValueError(f"links[{r}] = {l}: a leader is a row at or before its follower that leads itself")
+    links = [int(l) for l in links]
+    cols, mirror_col = mix_console.num_track_control_params, -1
+    if mirror_pan:
+        if cols != len(_desc.TRACK_INDEX):
+            raise ValueError(f"mirror_pan needs a console with {len(_desc.TRACK_INDEX)} track parameters (its pan column is mirrored); "
+                             f"{type(mix_console).__name__} has {cols}: pass mirror_pan=False")
+        if any(links.count(l) > 2 for l in set(links)):
+            raise ValueError("mirror_pan needs groups of at most two rows (a stereo pair): a pan has one mirror image")
+        mirror_col = _desc.TRACK_INDEX.index(("stereo_panner", "pan"))
+    return n_tracks, cols, mirror_col, links
+
+
+def _links_struct(links):
+    out = _cabi.LogitAdamLinks(segment=0, rows=links[0], cols=links[1], mirror_col=links[2])
+    for r, l in enumerate(links[3]):
+        out.leader[r] = l
+    return out
+
+
 def _segments(logits, params, grads):
     """The segment table of one call: a NULL gradient for a parameter the loss does not reach."""
     seg = (_cabi.LogitAdamSegment * len(logits))()
@@ -87,10 +150,11 @@ def _segments(logits, params, grads):
     return seg
 
 
-def _init(logits, params, items=None, sections=None):
+def _init(logits, params, items=None, sections=None, links=None):
     """p <- sigmoid(logits) by the kernel every later p comes from, and a zeroed optimiser state: one block, or with ``items`` one
     block per item of the leading dimension.  With ``sections`` one block, and ``params`` has that many equal rows per logit row;
-    with both, one block per item and ``items * sections`` rows, item-major."""
+    with both, one block per item and ``items * sections`` rows, item-major.  With ``links`` (a ``LogitAdamLinks``) the follower rows
+    of the track logits are first overwritten with their leaders' (DESIGN 25): one launch for every combination of the above."""
     lib = _hip.lib()
     dev = logits[0].device
     total = sum(t.numel() for t in logits)
@@ -103,7 +167,9 @@ def _init(logits, params, items=None, sections=None):
         raise ValueError(f"more parameters per fit than the logit-Adam kernel takes (2^20), or more than {_cabi.OPT_MAX_ITEMS} fits")
     state = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
     with _hip.launch_on(dev) as st:
-        if sections is not None and items is not None:
+        if links is not None:
+            lib.mst_logit_adam_init_linked(_segments(logits, params, none), len(logits), items or 1, sections or 1, links, state, st)
+        elif sections is not None and items is not None:
             lib.mst_logit_adam_init_sections_batch(_segments(logits, params, none), len(logits), items, sections, state, st)
         elif sections is not None:
             lib.mst_logit_adam_init_sections(_segments(logits, params, none), len(logits), sections, state, st)
@@ -238,9 +304,12 @@ class _Run:
     gives every parameter set ``S`` sections; with ``batched`` as well, ``items`` and ``sections`` are both set."""
 
     def __init__(self, tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-                 batch=None, batched=False, keep_best=False, patience=None, min_delta=0.0, poll_every=None, sectioned=False):
+                 batch=None, batched=False, keep_best=False, patience=None, min_delta=0.0, poll_every=None, sectioned=False, links=None,
+                 stereo_id=None, mirror_pan=True):
         self.keep_best = bool(keep_best)
         self.patience, self.min_delta, self.poll_every = _check_best(self.keep_best, patience, min_delta, poll_every)
+        links = _check_links(links, stereo_id, mirror_pan, tracks, mix_console)
+        self.links = None if links is None else _links_struct(links)  # rows of the track logits that share their settings
         is_profile = isinstance(ref_mix, AudioFeatureProfile)
         if not is_profile and not isinstance(ref_mix, torch.Tensor):
             raise TypeError(f"ref_mix must be a (2, n_samples) tensor or an AudioFeatureProfile, got {type(ref_mix).__name__}")
@@ -313,7 +382,7 @@ class _Run:
             # of sectioned fits, (B S, ...) leaves whose rows are equal within an item: the console runs at batch B S
             self.params = tuple(torch.empty(((B or 1) * self.sections,) + t.shape[1:], dtype=t.dtype, device=dev).requires_grad_(True)
                                 for t in self.logits)
-        self.state = _init(self.logits, self.params, B, self.sections)
+        self.state = _init(self.logits, self.params, B, self.sections, self.links)
         self.best = None
         if self.keep_best:  # all zero: no best yet
             per_item = sum(t.numel() for t in self.logits) // (B or 1)
@@ -352,7 +421,14 @@ class _Run:
                                              logits=self.logits))
         row = self.history.data_ptr() + 4 * n * self.history[0].numel()
         segments = _segments(self.logits, self.params, grads)
-        if B is None:
+        if self.links is not None:  # one call for single, batch, sections and best: the items' terms as a dense (items, n_terms)
+            adjacent = B is None and all(t.data_ptr() == terms[0].data_ptr() + 4 * k for k, t in enumerate(terms))
+            # (the one-element terms of a single fit usually are views of one buffer, side by side: no copy then)
+            dense = terms[0] if adjacent else torch.stack([t.detach().reshape(B or 1) for t in terms], dim=1)
+            with _hip.launch_on(self.tracks.device) as st:
+                lib.mst_logit_adam_step_linked(segments, len(self.logits), B or 1, self.sections or 1, self.links, dense, len(terms), row,
+                                               *self.hyper, self.min_delta, self.patience, self.state, self.best, st)
+        elif B is None:
             term_ptrs = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
             with _hip.launch_on(self.tracks.device) as st:
                 if self.sections is not None:  # the S gradient rows are summed inside the step
@@ -421,7 +497,7 @@ class _Run:
         with torch.no_grad():
             rows = (lambda t: t.shape) if self.sections is None else (lambda t: (B * self.sections,) + t.shape[1:])
             params = tuple(torch.empty(rows(t), dtype=t.dtype, device=t.device) for t in logits)
-            _init(logits, params, self.items, self.sections)
+            _init(logits, params, self.items, self.sections, self.links)  # consistent already: the followers keep their bits
             _, mix, track_dict, fx_dict, master_dict = self.console(self.tracks, *params, **self.flags)
             if self.items is not None and self.sections is not None:
                 mix, track_dict, fx_dict, master_dict = self._per_item(mix, track_dict, fx_dict, master_dict)
@@ -467,7 +543,8 @@ class _Run:
 
 
 def optimize(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, betas=(0.9, 0.999), eps=1e-8,
-             generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None, **console_flags):
+             generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None, links=None,
+             stereo_id=None, mirror_pan=True, **console_flags):
     """The reference's ``optimize`` (scripts/online.py:15-123): fit the console's parameters to ``ref_mix`` by Adam on their logits.
 
     ``tracks (T, N)`` and ``ref_mix (2, M)`` are device tensors (a CPU tensor raises, as everywhere in this package).  Every iteration
@@ -514,15 +591,29 @@ def optimize(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1
     ``keep_best``) freezes the fit once ``k`` iterations in a row have not improved: later iterations write their history row and
     nothing else.  ``poll_every=j`` (needs ``patience``) makes the host read the settled word every ``j`` iterations - a wait the caller
     asks for - and leave the loop when the fit has settled; the history is as long as the iterations that ran.
+
+    ``links`` / ``stereo_id`` tie rows of the track logits: the loaders split a stereo stem into two mono rows, and an
+    unlinked fit is free to EQ, compress and fade the two halves of an overhead pair differently and to pan both to one side.
+    ``links`` is a leader list of length ``T`` (``links[r]`` is the row whose settings row ``r`` shares, ``r`` itself if none;
+    a leader leads itself and stands before its followers), ``stereo_id`` the reference's flags (``links_from_stereo_id``); giving both
+    is a ``ValueError``.  The rows of a group share ONE set of logits: the init launch copies the leader's start point over its
+    followers (all ``T`` rows are still drawn, so the generator's stream is the script's), and every step forms the gradient of a shared
+    logit as the sum of its members' chained gradients, in member order in fp32, inside the same one launch
+    (``mst_logit_adam_step_linked``) and writes the new logit and parameter to every member.  ``mirror_pan=True`` (groups of at most
+    two rows, a console with the 27 track parameters) gives the follower MINUS the leader's pan logit, so its pan is ``1 - pan``
+    (reference mst/mixing.py:268-722).  The returned logits are full ``(1, T, 27)`` tensors and already consistent.  With neither
+    keyword the calls made are exactly those without this feature.  The same three keywords work in ``optimize_batch``,
+    ``optimize_sections`` and ``optimize_sections_batch``; one map serves every item of a batch.
     """
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-               keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every)
+               keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every,
+               links=links, stereo_id=stereo_id, mirror_pan=mirror_pan)
     return run.loop()
 
 
 def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, batch=None, betas=(0.9, 0.999),
                    eps=1e-8, generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None,
-                   **console_flags):
+                   links=None, stereo_id=None, mirror_pan=True, **console_flags):
     """``B`` independent ``optimize`` runs in the launches of one: random restarts, one song against several references, several songs
     against one reference.  One console forward at batch ``B``, ``loss_function.per_item``, one ``torch.autograd.grad`` with a ones
     cotangent per ``(B,)`` term and one ``mst_logit_adam_step_batch`` per iteration; nothing in the loop waits for the host.
@@ -546,7 +637,8 @@ def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001
     element; ``FloatingPointError`` is raised only when no item has a best iterate.  ``best_of(result)`` is the item with the lowest
     best loss - the random-restart recipe ranks restarts by that, not by the noise of the last step."""
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-               batch=batch, batched=True, keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every)
+               batch=batch, batched=True, keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every,
+               links=links, stereo_id=stereo_id, mirror_pan=mirror_pan)
     return run.loop()
 
 
@@ -566,7 +658,7 @@ def take_sections(tracks, starts, length):
 
 def optimize_sections(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, betas=(0.9, 0.999),
                       eps=1e-8, generator=None, callback=None, keep_best=False, patience=None, min_delta=0.0, poll_every=None,
-                      **console_flags):
+                      links=None, stereo_id=None, mirror_pan=True, **console_flags):
     """``optimize`` for ONE set of console parameters seen through ``S`` sections of the song at once: ``tracks`` is
     ``(S, T, n)`` (``take_sections``), the console runs at batch ``S`` with parameter leaves ``(S, T, 27)``, ``(S, 25)``, ``(S, 26)``
     whose rows are equal, ``loss_function.pooled(mix, target)`` turns the ``S`` rendered sections into ONE feature vector and one set
@@ -583,13 +675,14 @@ def optimize_sections(tracks, ref_mix, mix_console, loss_function, init_scale=0.
     Returns ``optimize``'s tuple with ``mix (S, 2, n)``, the dictionaries at batch ``S`` and the logits in ``optimize``'s shapes
     ``(1, T, 27)``, ``(1, 25)``, ``(1, 26)``, ready for ``render_blocks``.  ``S = 1`` against a profile is ``optimize`` bit for bit."""
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
-               keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every, sectioned=True)
+               keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every, sectioned=True,
+               links=links, stereo_id=stereo_id, mirror_pan=mirror_pan)
     return run.loop()
 
 
 def optimize_sections_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, batch=None,
                             betas=(0.9, 0.999), eps=1e-8, generator=None, callback=None, keep_best=False, patience=None,
-                            min_delta=0.0, poll_every=None, **console_flags):
+                            min_delta=0.0, poll_every=None, links=None, stereo_id=None, mirror_pan=True, **console_flags):
     """``B`` independent ``optimize_sections`` fits in the launches of one: restarts of a sectioned fit (``best_of`` keeps
     the best), one sectioned song against several references.  Per iteration one console forward at batch ``B S`` with parameter leaves
     ``(B S, T, 27)``, ``(B S, 25)``, ``(B S, 26)`` whose rows are equal within an item, ``loss_function.pooled(mix, target, items=B)``,
@@ -612,7 +705,8 @@ def optimize_sections_batch(tracks, ref_mix, mix_console, loss_function, init_sc
     ``render_blocks`` - and ``best_of(result)`` the item with the lowest best loss."""
     run = _Run(tracks, ref_mix, mix_console, loss_function, init_scale, lr, n_iters, betas, eps, generator, callback, console_flags,
                batch=batch, batched=True, keep_best=keep_best, patience=patience, min_delta=min_delta, poll_every=poll_every,
-               sectioned=True)
+               sectioned=True,
+               links=links, stereo_id=stereo_id, mirror_pan=mirror_pan)
     return run.loop()
 
 

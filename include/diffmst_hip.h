@@ -446,6 +446,40 @@ int mst_logit_adam_step_sections_batch(const mst_logit_adam_segment* segments, i
                                        double beta2, double eps, double min_delta, int32_t patience, void* state, void* best,
                                        void* stream);
 
+/* LINKED ROWS: the calls above for a fit in which groups of rows of one segment share one set of logits - the two
+ * channels of a stereo stem that the loaders split into two mono rows.  Per item that segment is dense (rows, cols); the members of a
+ * group are its rows in ascending order, the first is its leader, and leader[r] names the leader of row r.  At `mirror_col` a
+ * follower's logit is MINUS its leader's: sigmoid(-x) = 1 - sigmoid(x), the pan of the other channel.  The map is copied into the
+ * launch (it need not outlive the call) and is shared by all items.  `items`, `sections`, a nullable `best` and every other argument
+ * keep the meaning, layouts and sizes of mst_logit_adam_init_sections_batch / _step_sections_batch.
+ *   mst_logit_adam_init_linked  theta[f, c] <- theta[l, c] for every follower row f of leader l, -theta[l, c] at mirror_col (the
+ *                               negation is exact); then the state block zeroed and sigmoid(theta) written to every row of p
+ *   mst_logit_adam_step_linked  for the tied segment only the lane of a leader coordinate (l, c) acts.  Per member m: d_m the section
+ *                               sum over m's rows, g_m = (d_m (1 - p_m)) p_m with p_m from m's own row 0, negated for a follower at
+ *                               mirror_col; G = ((g_m0 + g_m1) + ...) in fp32 in member order; the Adam statements of
+ *                               mst_logit_adam_step on G for the leader's moments and logit; then theta, p = sigmoid of the member's
+ *                               own logit, and (on an improvement) the best block's logits before the update, for every member and
+ *                               every section row.  Followers' moment words stay zero.  An addend or a partial sum of G that is not
+ *                               finite stops the item's iteration like any non-finite gradient.  The other segments, and the tied one
+ *                               when its grad_p is NULL, take the path of the calls above.
+ * A map in which every row leads itself gives the bits of mst_logit_adam_init_sections_batch / _step_sections_batch in every output.
+ * A NULL `links`, a segment that is not in the table, rows outside [1, MST_OPT_MAX_LINK_ROWS], rows * cols different from the
+ * segment's per-item count, a leader[r] > r or one that does not lead itself, mirror_col outside [-1, cols) and every bad argument of
+ * the calls above return non-zero before anything is launched. */
+#define MST_OPT_MAX_LINK_ROWS 256
+typedef struct mst_logit_adam_links {
+    int32_t segment;    /* which segment is tied (the track tensor: 0) */
+    int32_t rows, cols; /* per item that segment is dense (rows, cols); rows * cols == its per-item count */
+    int32_t mirror_col; /* a follower's logit in this column is MINUS its leader's; -1: none */
+    uint8_t leader[MST_OPT_MAX_LINK_ROWS]; /* leader[r] <= r, leader[leader[r]] == leader[r]; leader[r] == r: r leads itself */
+} mst_logit_adam_links;
+int mst_logit_adam_init_linked(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, int32_t sections,
+                               const mst_logit_adam_links* links, void* state, void* stream);
+int mst_logit_adam_step_linked(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t items, int32_t sections,
+                               const mst_logit_adam_links* links, const float* loss_terms, int32_t n_terms, float* history_rows,
+                               double lr, double beta1, double beta2, double eps, double min_delta, int32_t patience, void* state,
+                               void* best, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * AudioFeatureLoss (reference mst/loss.py:198-260): five weighted MSE terms between features of
  * pred and target, both dense (bs, 2, n_samples): rms, crest factor, stereo width, stereo imbalance
