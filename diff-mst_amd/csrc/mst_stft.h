@@ -145,6 +145,90 @@ __device__ __forceinline__ void mrstft_final_body(const LossArgs& a, int tid, do
     }
 }
 
+// ---- per-item reduction: every group of R = rows / items consecutive rows a loss of its own -------------------------------------------
+// (resolution, row) entries the item reduction stages in LDS; above it the folds read the row sums from memory again
+constexpr int kItemStage = kMaxRes * 80;
+// LDS of one item reduction: the row sums and per-row ratios as mrstft_final_body stages them, and per (resolution, item) the item's
+// term of the loss and its two norm totals (the batch-global ratio's coefficients read those)
+struct ItemStage {
+    float4 srow[kItemStage];
+    double ratio[kItemStage];
+    double term[kItemStage];
+    double tot0[kItemStage], tot1[kItemStage];
+};
+// items losses + per-row backward coefficients by ONE wave (tid = 0..63): mrstft_final_body with every item "a batch of one" - `rows`
+// becomes R in every mean (a.count[] is filled with R by the host) and nothing is divided by `items`.  For items = 1 the expressions,
+// their order and their rounding points are those of mrstft_final_body, so the loss and the coefficients have its bits.  Every fold
+// has a fixed order (an item's rows ascending, then its resolutions ascending), staged or not.  a.loss: `items` floats.
+template <bool BLOCK_SYNC = true, bool AGENT = false>
+__device__ __forceinline__ void mrstft_items_body(const LossArgs& a, int items, int tid, ItemStage& st) {
+    auto sync = [] {
+        if (BLOCK_SYNC) __syncthreads();
+        else wave_lds_sync();
+    };
+    const int R = a.rows / items;
+    const bool staged = a.n_res * a.rows <= kItemStage;
+    // one lane per (resolution, row): fetch, roots, and - per-example ratio - the row's coefficients
+    for (int i = tid; i < a.n_res * a.rows; i += 64) {
+        const float4 sm = mrstft_load_sums<AGENT>(a.sums, i);
+        if (staged) st.srow[i] = sm;
+        if (a.sc_per_example) {
+            const double s0 = sqrt((double)sm.x), s1 = sqrt((double)sm.y);
+            if (staged) st.ratio[i] = s0 / s1;
+            double c_sc = a.w_sc / ((double)R * s0 * s1);
+            if (!(c_sc == c_sc) || c_sc > 1e30) c_sc = 0.0;  // identical signals: 0/0 -> no SC gradient
+            write_coef(a, i, i / a.rows, c_sc);
+        }
+    }
+    sync();
+    // item b's rows of one resolution, ascending in fp64 -> the resolution's term of l_b; t0 / t1: the item's two squared norms
+    auto fold = [&](int res, int b, double& t0, double& t1) {
+        double tot[4] = {0, 0, 0, 0}, sc_acc = 0.0;
+        for (int row = b * R; row < b * R + R; ++row) {
+            const int i = res * a.rows + row;
+            const float4 sm = staged ? st.srow[i] : mrstft_load_sums<AGENT>(a.sums, i);
+            tot[0] += (double)sm.x; tot[1] += (double)sm.y; tot[2] += (double)sm.z; tot[3] += (double)sm.w;
+            if (a.sc_per_example) sc_acc += staged ? st.ratio[i] : sqrt((double)sm.x) / sqrt((double)sm.y);  // same roots, same quotient
+        }
+        t0 = tot[0];
+        t1 = tot[1];
+        const double sc = a.sc_per_example ? sc_acc / R : sqrt(tot[0]) / sqrt(tot[1]);
+        return a.w_sc * sc + a.w_log * tot[2] / a.count[res] + a.w_lin * tot[3] / a.count[res];
+    };
+    if (staged) {  // one lane per (resolution, item); n_res * items <= n_res * rows entries
+        for (int e = tid; e < a.n_res * items; e += 64) {
+            double t0, t1;
+            st.term[e] = fold(e / items, e % items, t0, t1);
+            st.tot0[e] = t0;
+            st.tot1[e] = t1;
+        }
+        sync();
+    }
+    // one lane per item: its resolutions, ascending
+    for (int b = tid; b < items; b += 64) {
+        double total = 0.0;
+        for (int res = 0; res < a.n_res; ++res) {
+            double t0, t1;
+            total += staged ? st.term[res * items + b] : fold(res, b, t0, t1);
+        }
+        a.loss[b] = (float)(total / a.n_res);
+    }
+    if (a.sc_per_example) return;  // coefficients written in the staging loop
+    for (int i = tid; i < a.n_res * a.rows; i += 64) {
+        const int res = i / a.rows, b = (i % a.rows) / R;
+        double t0, t1;
+        if (staged) {
+            t0 = st.tot0[res * items + b];
+            t1 = st.tot1[res * items + b];
+        } else {
+            (void)fold(res, b, t0, t1);
+        }
+        double c_sc = a.w_sc * (double)a.world / (sqrt(t0) * sqrt(t1));
+        if (!(c_sc == c_sc) || c_sc > 1e30) c_sc = 0.0;  // identical signals: 0/0 -> no SC gradient
+        write_coef(a, i, res, c_sc);
+    }
+}
+
 struct StftArgs {
     const float* pred;     // (rows, n)
     const float* target;   // (rows, n)

@@ -592,6 +592,49 @@ __global__ __launch_bounds__(64) void k_mrstft_totals(LossArgs a) {
         a.totals[tid] = t;
     }
 }
+// ---- per-item losses (mst_mrstft_forward_items / _backward_items): groups of rows / items consecutive rows, each a loss of its own ----
+// stage 2 of the two-launch form: `items` losses + per-row backward coefficients (mrstft_items_body, mst_stft.h)
+__global__ __launch_bounds__(64) void k_mrstft_final_items(LossArgs a, int items) {
+    __shared__ ItemStage st;
+    mrstft_items_body(a, items, threadIdx.x, st);
+}
+// stages 1 + 2 in one launch: k_mrstft_finish - its row fold, its ticket and its hand-over, branch for branch - with the item
+// reduction as the last workgroup's body
+__global__ __launch_bounds__(64) void k_mrstft_finish_items(LossArgs a, unsigned* ticket, int items) {
+    __shared__ ItemStage st;
+    __shared__ unsigned mine;
+#if MST_FINISH_FENCES
+    mrstft_rowsum(a, blockIdx.x, blockIdx.y, threadIdx.x);
+    __threadfence();
+    if (threadIdx.x == 0) mine = atomicAdd(ticket, 1u);
+    __syncthreads();
+    if (mine != gridDim.x * gridDim.y - 1) return;
+    __threadfence();
+    mrstft_items_body(a, items, threadIdx.x, st);
+#else
+    mrstft_rowsum<true>(a, blockIdx.x, blockIdx.y, threadIdx.x);
+    if (threadIdx.x == 0) {
+#if defined(__clang__)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        mine = atomicAdd(ticket, 1u);
+    }
+    __syncthreads();
+    if (mine != gridDim.x * gridDim.y - 1) return;
+    mrstft_items_body<true, true>(a, items, threadIdx.x, st);
+#endif
+}
+// the per-row coefficients of the forward times the row's item's cotangent, each ONE fp32 product (what the backward kernels form
+// as coef * grad_loss[0]), into the second coefficient slab; the backward launches then multiply by *one = 1.0f, which is exact
+__global__ __launch_bounds__(256) void k_mrstft_scale_items(const float* __restrict__ coef, const float* __restrict__ g,
+                                                            float* __restrict__ scaled, float* one, int n_res, int rows, int per_item) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) one[0] = 1.0f;
+    if (i >= n_res * rows) return;
+    const float gi = g[(i % rows) / per_item];
+    const float4 c = *reinterpret_cast<const float4*>(coef + (int64_t)i * 4);
+    *reinterpret_cast<float4*>(scaled + (int64_t)i * 4) = make_float4(c.x * gi, c.y * gi, c.z * gi, 0.f);
+}
 }  // namespace mst
 
 // ======================================================================================= C ABI
@@ -676,7 +719,7 @@ Plan make_plan(const mst_mrstft_desc* d) {
     p.sums_off = p.part_total;
     p.coef_off = p.sums_off + round_up((int64_t)d->n_res * d->rows * 4, 64);
     p.coefs_off = p.coef_off + round_up((int64_t)d->n_res * d->rows * 4, 64);
-    p.tick_off = p.coefs_off + round_up((int64_t)d->n_res * d->rows * 4, 64);  // rows + 1 tickets of the fused reduction (mst_stft.h)
+    p.tick_off = p.coefs_off + round_up((int64_t)d->n_res * d->rows * 4, 64);  // 64 words: [0] the ticket of the fused reduction, [1] the 1.0f of mst_mrstft_backward_items
     p.seam_off = p.tick_off + 64;
     p.ws_floats = p.seam_off;
     // backward seam hand-over (mst_stft.h): exactly one seam-mode resolution, at least one halo-mode one, all on the round-2 kernels
@@ -739,9 +782,10 @@ extern "C" int mst_mrstft_init_tables(const mst_mrstft_desc* d, void* tables, vo
 }
 
 // The argument block of resolution i as every transform launch takes it: inputs, tables, the resolution, its partial sums and kept
-// planes (where the plan has them).  With grad_pred (the backward): + the row sums / backward coefficients and the cotangents.
+// planes (where the plan has them).  With grad_pred (the backward): + the row sums / backward coefficients and the cotangents;
+// coef: the (n_res, rows, 4) coefficient block the launch reads (null: the one the forward wrote, at coef_off).
 static StftArgs stft_args(const Plan& p, const mst_mrstft_desc* d, int i, const float* pred, const float* target, const void* tables, float* ws,
-                          const float* grad_loss = nullptr, float* grad_pred = nullptr) {
+                          const float* grad_loss = nullptr, float* grad_pred = nullptr, const float* coef = nullptr) {
     StftArgs a{};
     a.pred = pred;
     a.target = target;
@@ -754,7 +798,7 @@ static StftArgs stft_args(const Plan& p, const mst_mrstft_desc* d, int i, const 
     a.xspec = p.xspec_off[i] >= 0 ? ws + p.xspec_off[i] : nullptr;
     if (grad_pred) {
         a.sums = ws + p.sums_off + (int64_t)i * d->rows * 4;
-        a.coef = ws + p.coef_off + (int64_t)i * d->rows * 4;
+        a.coef = (coef ? coef : ws + p.coef_off) + (int64_t)i * d->rows * 4;
         a.grad_loss = grad_loss;
         a.grad_pred = grad_pred;
     } else {
@@ -764,9 +808,11 @@ static StftArgs stft_args(const Plan& p, const mst_mrstft_desc* d, int i, const 
 }
 
 // stages: 1 = transforms + row sums (+ totals when asked for), 2 = loss + backward coefficients
+// items > 0: `loss` takes one value per group of rows / items consecutive rows (mst_mrstft_forward_items); the transform launches are
+// those of items = 0, the reduction behind them is the item reduction (same launch count)
 static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables, float* loss,
                                  double* totals, const double* gtotals, int world, int stages, void* workspace,
-                                 size_t workspace_bytes, void* stream_, bool keep = true) {
+                                 size_t workspace_bytes, void* stream_, bool keep = true, int items = 0) {
     Plan p = make_plan(d);
     if (!keep) {  // evaluation only (mst_mrstft_forward_eval): nothing is kept for a backward, the planes are not written
         for (int i = 0; i < kMaxRes; ++i) p.ymag_off[i] = p.xspec_off[i] = -1;
@@ -797,7 +843,7 @@ static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, co
     for (int i = 0; i < d->n_res; ++i) {
         la.n_groups[i] = p.n_groups[i];
         la.part_off[i] = p.part_off[i];
-        la.count[i] = (float)((double)d->rows * p.res[i].n_bins * p.res[i].n_frames);
+        la.count[i] = (float)((double)(items > 0 ? d->rows / items : d->rows) * p.res[i].n_bins * p.res[i].n_frames);
     }
     // the reference's three resolutions, all on the round-2 kernels: ONE forward launch (k_stft3_fwd, mst_stft2.hip)
     int role[3] = {-1, -1, -1};
@@ -833,14 +879,19 @@ static int mrstft_forward_stages(const mst_mrstft_desc* d, const float* pred, co
             MST_FOR_NFFT(a.r.n_fft, MST_LAUNCH_FWD)
     }
     if (fuse) {
-        hipLaunchKernelGGL(k_mrstft_finish, dim3(d->rows, d->n_res), dim3(64), 0, stream, la, reinterpret_cast<unsigned*>(ws + p.tick_off));
+        if (items > 0)
+            hipLaunchKernelGGL(k_mrstft_finish_items, dim3(d->rows, d->n_res), dim3(64), 0, stream, la,
+                               reinterpret_cast<unsigned*>(ws + p.tick_off), items);
+        else
+            hipLaunchKernelGGL(k_mrstft_finish, dim3(d->rows, d->n_res), dim3(64), 0, stream, la, reinterpret_cast<unsigned*>(ws + p.tick_off));
         return (int)hipGetLastError();
     }
     if (stages & 1) {
         hipLaunchKernelGGL(k_mrstft_rowsums, dim3(d->rows, d->n_res), dim3(64), 0, stream, la);
         if (totals) hipLaunchKernelGGL(k_mrstft_totals, dim3(1), dim3(64), 0, stream, la);
     }
-    if (stages & 2) hipLaunchKernelGGL(k_mrstft_final, dim3(1), dim3(64), 0, stream, la);
+    if ((stages & 2) && items > 0) hipLaunchKernelGGL(k_mrstft_final_items, dim3(1), dim3(64), 0, stream, la, items);
+    else if (stages & 2) hipLaunchKernelGGL(k_mrstft_final, dim3(1), dim3(64), 0, stream, la);
     return (int)hipGetLastError();
 }
 
@@ -852,6 +903,18 @@ extern "C" int mst_mrstft_forward_eval(const mst_mrstft_desc* d, const float* pr
                                        float* loss, void* workspace, size_t workspace_bytes, void* stream) {
     return mrstft_forward_stages(d, pred, target, tables, loss, nullptr, nullptr, 1, 3, workspace, workspace_bytes, stream, false);
 }
+// `items` groups of rows / items consecutive rows, item-major; anything else is refused before a launch
+static bool mrstft_items_ok(const mst_mrstft_desc* d, int32_t items) { return d && items >= 1 && d->rows > 0 && d->rows % items == 0; }
+extern "C" int mst_mrstft_forward_items(const mst_mrstft_desc* d, int32_t items, const float* pred, const float* target, const void* tables,
+                                        float* losses, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!mrstft_items_ok(d, items)) return hipErrorInvalidValue;
+    return mrstft_forward_stages(d, pred, target, tables, losses, nullptr, nullptr, 1, 3, workspace, workspace_bytes, stream, true, items);
+}
+extern "C" int mst_mrstft_forward_items_eval(const mst_mrstft_desc* d, int32_t items, const float* pred, const float* target,
+                                             const void* tables, float* losses, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!mrstft_items_ok(d, items)) return hipErrorInvalidValue;
+    return mrstft_forward_stages(d, pred, target, tables, losses, nullptr, nullptr, 1, 3, workspace, workspace_bytes, stream, false, items);
+}
 extern "C" int mst_mrstft_forward_partial(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables,
                                           double* totals, void* workspace, size_t workspace_bytes, void* stream) {
     if (!totals) return hipErrorInvalidValue;
@@ -862,14 +925,11 @@ extern "C" int mst_mrstft_forward_finish(const mst_mrstft_desc* d, const double*
     return mrstft_forward_stages(d, nullptr, nullptr, nullptr, loss, nullptr, global_totals, world, 2, workspace, workspace_bytes, stream);
 }
 
-extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables,
-                                   const float* grad_loss, float* grad_pred, void* workspace, size_t workspace_bytes,
-                                   void* stream_) {
-    const Plan p = make_plan(d);
-    if (!p.ok || !pred || !target || !tables || !grad_loss || !grad_pred || !workspace) return hipErrorInvalidValue;
-    if (workspace_bytes < (size_t)p.ws_floats * sizeof(float)) return hipErrorInvalidValue;
-    hipStream_t stream = (hipStream_t)stream_;
-    float* ws = (float*)workspace;
+// The backward's launches: every transform launch reads coef[row] * grad_loss[0] (coef: see stft_args) and the sequence leaves
+// grad_pred (rows, n) written.  Shared by mst_mrstft_backward (the forward's coefficients, the caller's cotangent) and
+// mst_mrstft_backward_items (coefficients already times each item's cotangent, a device 1.0f).
+static int mrstft_backward_launches(const Plan& p, const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables,
+                                    const float* coef, const float* grad_loss, float* grad_pred, float* ws, hipStream_t stream) {
     bool all2 = true;
     for (int i = 0; i < d->n_res; ++i) all2 = all2 && p.engine2[i];
     if (all2) {
@@ -904,7 +964,7 @@ extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, 
         for (int k = 0; k < n_order; ++k) {
             const int i = order[k];
             const bool halo = k >= n_seam;
-            StftArgs a = stft_args(p, d, i, pred, target, tables, ws, grad_loss, grad_pred);
+            StftArgs a = stft_args(p, d, i, pred, target, tables, ws, grad_loss, grad_pred, coef);
             a.accumulate = (halo && written) ? 1 : 0;
             if (handover && (!halo || pending)) {
                 const ResInfo& sr = p.res[p.seam_res];
@@ -927,7 +987,7 @@ extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, 
     }
     (void)hipMemsetAsync(grad_pred, 0, (size_t)d->rows * d->n_samples * sizeof(float), stream);
     for (int i = 0; i < d->n_res; ++i) {
-        StftArgs a = stft_args(p, d, i, pred, target, tables, ws, grad_loss, grad_pred);
+        StftArgs a = stft_args(p, d, i, pred, target, tables, ws, grad_loss, grad_pred, coef);
         a.ymag = a.xspec = nullptr;  // the generic kernels recompute the transforms: no kept planes
         // three LDS buffers (pairing two frames per inverse FFT) fit up to n_fft = 4096; 8192 runs one frame per workgroup
         const bool pair = a.r.n_fft <= 4096;
@@ -943,4 +1003,31 @@ extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, 
             MST_FOR_NFFT(a.r.n_fft, MST_LAUNCH_BWD)
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables,
+                                   const float* grad_loss, float* grad_pred, void* workspace, size_t workspace_bytes,
+                                   void* stream_) {
+    const Plan p = make_plan(d);
+    if (!p.ok || !pred || !target || !tables || !grad_loss || !grad_pred || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.ws_floats * sizeof(float)) return hipErrorInvalidValue;
+    return mrstft_backward_launches(p, d, pred, target, tables, nullptr, grad_loss, grad_pred, (float*)workspace, (hipStream_t)stream_);
+}
+
+// after mst_mrstft_forward_items on the same workspace: k_mrstft_scale_items fills the plan's second coefficient slab and parks 1.0f in
+// word 1 of the ticket region (the forward uses word 0 alone), then the launches of mst_mrstft_backward
+extern "C" int mst_mrstft_backward_items(const mst_mrstft_desc* d, int32_t items, const float* pred, const float* target, const void* tables,
+                                         const float* grad_losses, float* grad_pred, void* workspace, size_t workspace_bytes,
+                                         void* stream_) {
+    if (!mrstft_items_ok(d, items)) return hipErrorInvalidValue;
+    const Plan p = make_plan(d);
+    if (!p.ok || !pred || !target || !tables || !grad_losses || !grad_pred || !workspace) return hipErrorInvalidValue;
+    if (workspace_bytes < (size_t)p.ws_floats * sizeof(float)) return hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    float* ws = (float*)workspace;
+    float* one = ws + p.tick_off + 1;
+    const int entries = d->n_res * d->rows;
+    hipLaunchKernelGGL(k_mrstft_scale_items, dim3((entries + 255) / 256), dim3(256), 0, stream, ws + p.coef_off, grad_losses,
+                       ws + p.coefs_off, one, d->n_res, d->rows, d->rows / items);
+    return mrstft_backward_launches(p, d, pred, target, tables, ws + p.coefs_off, one, grad_pred, ws, stream);
 }

@@ -196,6 +196,9 @@ SIGNATURES = {
     "mst_mrstft_forward_partial": (STATUS, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_mrstft_forward_finish": (STATUS, [C.POINTER(MrstftDesc), _P, C.c_int32, _P, _P, C.c_size_t, _S]),
     "mst_mrstft_backward": (STATUS, [C.POINTER(MrstftDesc), _P, _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_forward_items": (STATUS, [C.POINTER(MrstftDesc), C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_forward_items_eval": (STATUS, [C.POINTER(MrstftDesc), C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _S]),
+    "mst_mrstft_backward_items": (STATUS, [C.POINTER(MrstftDesc), C.c_int32, _P, _P, _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_peak_normalize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "mst_peak_normalize_forward": (STATUS, [_P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _S]),
     "mst_peak_normalize_backward": (STATUS, [_P, _P, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _S]),

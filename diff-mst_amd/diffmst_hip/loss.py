@@ -110,6 +110,65 @@ class _MrstftFunction(torch.autograd.Function):
         return gx.view(ctx.shape), None, None, None
 
 
+def _mrstft_check_items(items, rows):
+    """``items`` groups of consecutive rows of the leading dimension: a positive whole number that divides it -> that number."""
+    if isinstance(items, bool) or int(items) != items or int(items) < 1:
+        raise ValueError(f"items must be a positive whole number, got {items!r}")
+    if rows % int(items):
+        raise ValueError(f"the input's leading dimension is {rows}, which items={items} does not divide (rows are item-major)")
+    return int(items)
+
+
+class _MrstftItemsFunction(torch.autograd.Function):
+    """``_MrstftFunction`` with every group of ``shape[0] / items`` leading entries a loss of its own: an ``(items,)`` output, a
+    cotangent per item (``mst_mrstft_forward_items`` / ``_backward_items``)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, cfg, items, want_grad=True):
+        _hip.require_cuda(pred, target)
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("MultiResolutionSTFTLoss (MI355X build): the target's gradient is not implemented; detach the target")
+        want_grad = bool(want_grad) and ctx.needs_input_grad[0]
+        ctx.saved = False
+        lib = _hip.lib()
+        n = pred.shape[-1]
+        x = pred.float().reshape(-1, n).contiguous()
+        y = target.float().reshape(-1, n).contiguous()
+        if x.shape != y.shape:
+            raise ValueError(f"input {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+        dev = x.device
+        desc = _mrstft_desc(x.shape[0], n, cfg["resolutions"], cfg["w_sc"], cfg["w_log_mag"], cfg["w_lin_mag"],
+                            cfg["sc_per_example"], cfg["eps"])
+        tables = _tables(desc, cfg["resolutions"], dev)
+        nbytes = lib.mst_mrstft_workspace_bytes(desc)
+        if nbytes == 0:
+            raise ValueError("unsupported STFT configuration for this input length")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        losses = torch.empty(items, dtype=torch.float32, device=dev)
+        # no gradient asked for (torch.no_grad(), a detached prediction): the values only - the forward then keeps no spectra
+        fwd = lib.mst_mrstft_forward_items if want_grad else lib.mst_mrstft_forward_items_eval
+        with _hip.launch_on(dev) as st:
+            fwd(desc, items, x, y, tables, losses, ws, nbytes, st)
+        if want_grad:
+            ctx.desc, ctx.nbytes, ctx.shape, ctx.items = desc, nbytes, pred.shape, items
+            ctx.save_for_backward(x, y, tables, ws)
+            ctx.saved = True
+        return losses
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_losses):
+        if not ctx.saved:  # nothing was kept (value-only forward): there is no gradient to hand back
+            return None, None, None, None, None
+        x, y, tables, ws = ctx.saved_tensors
+        lib = _hip.lib()
+        g = grad_losses.float().reshape(ctx.items).contiguous()
+        gx = torch.empty_like(x)
+        with _hip.launch_on(x.device) as st:
+            lib.mst_mrstft_backward_items(ctx.desc, ctx.items, x, y, tables, g, gx, ws, ctx.nbytes, st)
+        return gx.view(ctx.shape), None, None, None, None
+
+
 class MultiResolutionSTFTLoss(torch.nn.Module):
     """auraloss-compatible multi-resolution STFT loss (spectral convergence + log / linear magnitude L1).
 
@@ -158,8 +217,46 @@ class MultiResolutionSTFTLoss(torch.nn.Module):
             sync_group=sync_group,
         )
 
+    # sample against sample: no profile of a reference stands in for it.  mst.online's sectioned fits read this and hand the
+    # reference itself to ``pooled``, cut like the tracks
+    paired = True
+
     def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         return _MrstftFunction.apply(x, y, self.cfg, torch.is_grad_enabled())
+
+    def per_item(self, input: torch.Tensor, target: torch.Tensor, items: int = None) -> torch.Tensor:
+        """The loss of every item on its own: an ``(items,)`` float32 device tensor, element ``b`` what ``forward`` returns for item
+        ``b``'s part of ``input`` and ``target`` alone, differentiable in ``input``; a cotangent on element ``b`` reaches item ``b``
+        only, and no gradient carries a ``1 / items`` (``AudioFeatureLoss.per_item``'s convention: under the batch mean Adam's ``eps``
+        makes that factor visible).  ``input`` and ``target`` have ``forward``'s shapes, ``(bs, chs, n)``; ``items`` defaults to
+        ``bs`` and must divide it: item ``b`` is ``input[b * bs / items:(b + 1) * bs / items]``, all channels - with
+        ``sc_per_example=False`` the ratio is taken over the item's rows.  One pass over the batch (``mst_mrstft_forward_items``):
+        ``forward``'s transform launches, then a reduction that folds in a fixed order, so equal inputs give equal bits and
+        ``items=1`` gives ``forward``'s.  For per-song validation figures and for a batch of independent fits
+        (``mst.online.optimize_batch``).
+
+        Under ``torch.no_grad()`` or with a detached ``input`` only the values are computed and nothing is kept.  The target's
+        gradient is refused, as in ``forward``; so is ``sync_group``: a ratio over the rows of every rank has no per-item meaning."""
+        if self.cfg.get("sync_group") is not None:
+            raise ValueError("MultiResolutionSTFTLoss.per_item / pooled: not with sync_group - a ratio formed over the rows of every "
+                             "rank has no per-item meaning; build the loss without it")
+        if not isinstance(input, torch.Tensor) or not isinstance(target, torch.Tensor):
+            raise TypeError("MultiResolutionSTFTLoss.per_item takes two tensors")
+        if target.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("MultiResolutionSTFTLoss (MI355X build): the target's gradient is not implemented; detach the target")
+        if input.dim() < 2:
+            raise ValueError(f"per_item takes an input of shape (bs, ..., n), got {tuple(input.shape)}")
+        if input.shape != target.shape:
+            raise ValueError(f"input {tuple(input.shape)} and target {tuple(target.shape)} differ")
+        items = _mrstft_check_items(input.shape[0] if items is None else items, input.shape[0])
+        return _MrstftItemsFunction.apply(input, target, self.cfg, items, torch.is_grad_enabled())
+
+    def pooled(self, input: torch.Tensor, target: torch.Tensor, items: int = 1) -> torch.Tensor:
+        """``per_item`` with ``items`` defaulting to 1: the ``S`` sections of one fit, ``input (S, 2, n)``, are ONE item of ``2 S`` rows
+        and the result is ``(1,)``.  For this loss every term is a mean over rows (or a ratio of sums over them), so pooling the
+        sections is the loss of the sections taken as one batch.  ``items=B``: ``input`` is ``(B * S, 2, n)``, item-major, and the
+        result ``(B,)`` (``mst.online.optimize_sections`` / ``optimize_sections_batch``).  ``target`` is cut like ``input``."""
+        return self.per_item(input, target, items)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -192,11 +192,35 @@ def _check_single(tracks, ref_mix, is_profile):
     return None
 
 
+def _is_paired(loss_function):
+    """A paired loss compares the mix with the reference sample against sample (``MultiResolutionSTFTLoss``): it has no ``profile``
+    method and says so with ``paired = True``.  A sectioned fit hands it the reference itself, which must then be cut like the tracks.
+    (The attribute, not the missing method alone, decides: a loss with ``pooled`` and neither of the two keeps the reference forms
+    and the errors it has always had.)"""
+    return not hasattr(loss_function, "profile") and bool(getattr(loss_function, "paired", False))
+
+
+def _check_paired_needs_no_profile(name, method, ref_mix, is_profile, loss_function, n_samples=None):
+    """What only a loss with a ``profile`` method can be fitted to - a stored ``AudioFeatureProfile``, or (``n_samples`` given: the
+    fits that would profile it) a reference of another length than the tracks - is refused for a paired loss as the missing method
+    it is, before anything touches the device."""
+    if not _is_paired(loss_function):
+        return
+    cls = type(loss_function).__name__
+    if is_profile:
+        raise TypeError(f"{name}: {cls}.{method} is paired (sample against sample) and takes a reference tensor, not an "
+                        f"AudioFeatureProfile: a profile needs a loss_function with a profile method (AudioFeatureLoss), {cls} has none")
+    if n_samples is not None and ref_mix.shape[-1] != n_samples:
+        raise TypeError(f"{name}: a reference of {ref_mix.shape[-1]} samples against tracks of {n_samples} has to be profiled, which needs "
+                        f"a loss_function with a profile method (AudioFeatureLoss): {cls} has none - {cls}.{method} is paired (sample "
+                        "against sample) and takes a reference of the tracks' length")
+
+
 def _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch):
     """Types and shapes of ``optimize_batch``, before anything touches the device -> (B, init scales)."""
     if not callable(getattr(loss_function, "per_item", None)):
-        raise TypeError("optimize_batch needs a loss_function with a per_item(input, target) method (AudioFeatureLoss.per_item): "
-                        f"{type(loss_function).__name__} has none")
+        raise TypeError("optimize_batch needs a loss_function with a per_item(input, target) method (AudioFeatureLoss.per_item, "
+                        f"MultiResolutionSTFTLoss.per_item): {type(loss_function).__name__} has none")
     if not isinstance(tracks, torch.Tensor) or tracks.dim() not in (2, 3):
         raise ValueError("tracks must be (B, n_tracks, n_samples), or (n_tracks, n_samples) with batch=B")
     if tracks.dim() == 3:
@@ -214,6 +238,7 @@ def _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch):
             raise ValueError(f"a profile given as ref_mix must have batch size {B} or 1, got {ref_mix.batch_size}")
     elif not (ref_mix.dim() == 2 and ref_mix.shape[0] == 2) and not (ref_mix.dim() == 3 and tuple(ref_mix.shape[:2]) == (B, 2)):
         raise ValueError(f"ref_mix must be ({B}, 2, n_samples), (2, n_samples) or an AudioFeatureProfile, got {tuple(ref_mix.shape)}")
+    _check_paired_needs_no_profile("optimize_batch", "per_item", ref_mix, is_profile, loss_function, tracks.shape[-1])
     if isinstance(init_scale, (int, float)):
         scales = [float(init_scale)] * B
     else:
@@ -224,17 +249,32 @@ def _check_batch(tracks, ref_mix, is_profile, loss_function, init_scale, batch):
     return B, scales
 
 
+def _check_paired_sections(ref_mix, loss_function, S, n_samples, B=None):
+    """The reference of a sectioned fit under a paired loss, before anything touches the device: ``(S, 2, n)`` - one for every item of
+    a batch - or, for a batch, ``(B, S, 2, n)``."""
+    shape, forms = tuple(ref_mix.shape), f"({S}, 2, {n_samples})"
+    if B is not None:
+        forms += f" or ({B}, {S}, 2, {n_samples})"
+    if shape != (S, 2, n_samples) and (B is None or shape != (B, S, 2, n_samples)):
+        raise ValueError(f"{type(loss_function).__name__} is a paired loss (sample against sample: it has no profile) and needs a "
+                         f"reference cut like the tracks: ref_mix {forms}, as take_sections cuts a (2, n_samples) reference with the "
+                         f"tracks' starts and length - got {shape}")
+
+
 def _check_sections(tracks, ref_mix, is_profile, loss_function):
     """Types and shapes of ``optimize_sections``, before anything touches the device -> S."""
     if not callable(getattr(loss_function, "pooled", None)):
-        raise TypeError("optimize_sections needs a loss_function with a pooled(input, target) method (AudioFeatureLoss.pooled): "
-                        f"{type(loss_function).__name__} has none")
+        raise TypeError("optimize_sections needs a loss_function with a pooled(input, target) method (AudioFeatureLoss.pooled, "
+                        f"MultiResolutionSTFTLoss.pooled): {type(loss_function).__name__} has none")
     if not isinstance(tracks, torch.Tensor) or tracks.dim() != 3:
         raise ValueError("tracks must be (S, n_tracks, n_samples): S sections of one song (take_sections cuts them)")
     S = tracks.shape[0]
     if not 1 <= S <= _cabi.OPT_MAX_SECTIONS:
         raise ValueError(f"the number of sections must be 1..{_cabi.OPT_MAX_SECTIONS}, got {S}")
-    if is_profile:
+    _check_paired_needs_no_profile("optimize_sections", "pooled", ref_mix, is_profile, loss_function)
+    if _is_paired(loss_function):
+        _check_paired_sections(ref_mix, loss_function, S, tracks.shape[-1])
+    elif is_profile:
         if ref_mix.batch_size != 1:
             raise ValueError(f"a profile given as ref_mix must have batch size 1, got {ref_mix.batch_size}")
     elif not (ref_mix.dim() == 2 and ref_mix.shape[0] == 2) and not (ref_mix.dim() == 3 and ref_mix.shape[1] == 2):
@@ -258,7 +298,7 @@ def _check_sections_batch(tracks, ref_mix, is_profile, loss_function, init_scale
     pooled = getattr(loss_function, "pooled", None)
     if not callable(pooled) or not _takes_items(pooled):
         raise TypeError("optimize_sections_batch needs a loss_function with a pooled(input, target, items=B) method "
-                        f"(AudioFeatureLoss.pooled): {type(loss_function).__name__} has none")
+                        f"(AudioFeatureLoss.pooled, MultiResolutionSTFTLoss.pooled): {type(loss_function).__name__} has none")
     if not isinstance(tracks, torch.Tensor) or tracks.dim() not in (3, 4):
         raise ValueError("tracks must be (B, S, n_tracks, n_samples), or (S, n_tracks, n_samples) with batch=B")
     if tracks.dim() == 4:
@@ -274,7 +314,10 @@ def _check_sections_batch(tracks, ref_mix, is_profile, loss_function, init_scale
         raise ValueError(f"the batch size must be 1..{_cabi.OPT_MAX_ITEMS}, got {B}")
     if not 1 <= S <= _cabi.OPT_MAX_SECTIONS:
         raise ValueError(f"the number of sections must be 1..{_cabi.OPT_MAX_SECTIONS}, got {S}")
-    if is_profile:
+    _check_paired_needs_no_profile("optimize_sections_batch", "pooled", ref_mix, is_profile, loss_function)
+    if _is_paired(loss_function):
+        _check_paired_sections(ref_mix, loss_function, S, tracks.shape[-1], B)
+    elif is_profile:
         if ref_mix.batch_size not in (1, B):
             raise ValueError(f"a profile given as ref_mix must have batch size {B} or 1, got {ref_mix.batch_size}")
     elif not (ref_mix.dim() == 2 and ref_mix.shape[0] == 2) and not (ref_mix.dim() == 3 and tuple(ref_mix.shape[:2]) == (B, 2)) and not (
@@ -346,14 +389,21 @@ class _Run:
         elif self.sections is not None and B is not None:
             # analysed here, once: one reference for every item, one per item, or one per item given as R sections and pooled
             ref = ref_mix.detach()
-            if ref.dim() == 4:
+            if _is_paired(loss_function):
+                # a paired loss has no profile: it gets the reference itself, flattened item-major like the mix it meets, (B S, 2, n)
+                rows = ref if ref.dim() == 4 else ref.unsqueeze(0).expand(B, -1, -1, -1)
+                self.ref_mix = rows.reshape(B * self.sections, 2, n_samples).contiguous()
+            elif ref.dim() == 4:
                 self.ref_mix = loss_function.profile(ref.reshape((-1,) + tuple(ref.shape[2:])), pool=True, items=B)
             else:
                 self.ref_mix = loss_function.profile(ref.unsqueeze(0) if ref.dim() == 2 else ref)
         elif self.sections is not None:
             # the pooled loss has no paired route: the reference is analysed here, once - its sections pooled if it comes as sections
             ref = ref_mix.detach()
-            self.ref_mix = loss_function.profile(ref, pool=True) if ref.dim() == 3 else loss_function.profile(ref.unsqueeze(0))
+            if _is_paired(loss_function):  # the reference itself, (S, 2, n): section s of it meets section s of the mix
+                self.ref_mix = ref.contiguous()
+            else:
+                self.ref_mix = loss_function.profile(ref, pool=True) if ref.dim() == 3 else loss_function.profile(ref.unsqueeze(0))
         else:
             self.ref_mix = ref_mix.detach()
             if self.ref_mix.dim() == 2:
@@ -620,8 +670,13 @@ def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001
 
     ``tracks`` is ``(B, T, N)``, or ``(T, N)`` with ``batch=B`` (the song is repeated).  ``ref_mix`` is ``(B, 2, M)``, ``(2, M)`` (one
     reference for every item) or an ``AudioFeatureProfile`` of batch size ``B`` or 1; a tensor is profiled once, before the loop.
-    ``loss_function`` must offer ``per_item(input, target)`` -> ``(B,)`` terms (``AudioFeatureLoss.per_item``): with a batch-mean loss
-    every item's gradient would carry ``1 / B``, which Adam's ``eps`` makes visible.  ``init_scale`` is a number or ``B`` numbers.  Item
+    ``loss_function`` must offer ``per_item(input, target)`` -> ``(B,)`` terms (``AudioFeatureLoss.per_item``,
+    ``MultiResolutionSTFTLoss.per_item``): with a batch-mean loss every item's gradient would carry ``1 / B``, which Adam's ``eps`` makes
+    visible.  A loss without a ``profile`` method (the paired ``MultiResolutionSTFTLoss``: recreating an existing mix of the same
+    stems, where restarts matter because the spectrogram loss is far from convex in the EQ and compressor settings) is handed the
+    reference itself, ``(B, 2, N)`` - one ``(2, N)`` reference is repeated - and returns one ``(B,)`` tensor: the history then has the
+    ``"loss"`` column alone; a profile, or a reference of another length than the tracks, needs the ``profile`` method such a loss
+    lacks and is a ``TypeError``.  ``init_scale`` is a number or ``B`` numbers.  Item
     ``b`` starts at the ``b``-th successive ``start_point()`` draw from the generator, so ``B = 1`` starts where ``optimize`` starts.
 
     Returns ``optimize``'s 8-tuple with a leading batch dimension everywhere, plus ``stopped_at``: ``mix (B, 2, N)``, logits
@@ -644,7 +699,8 @@ def optimize_batch(tracks, ref_mix, mix_console, loss_function, init_scale=0.001
 
 def take_sections(tracks, starts, length):
     """``tracks (T, N)`` -> the contiguous ``(S, T, length)`` tensor of the sections ``tracks[:, start:start + length]``, one per entry
-    of ``starts``, on the device of ``tracks``: what ``optimize_sections`` takes."""
+    of ``starts``, on the device of ``tracks``: what ``optimize_sections`` takes.  A ``(2, N)`` reference mix is cut the same way, into
+    the ``(S, 2, length)`` reference a paired loss (``MultiResolutionSTFTLoss``) needs beside tracks cut with the same ``starts``."""
     if not isinstance(tracks, torch.Tensor) or tracks.dim() != 2:
         raise ValueError("tracks must be (n_tracks, n_samples)")
     starts, length = [int(v) for v in starts], int(length)
@@ -668,9 +724,12 @@ def optimize_sections(tracks, ref_mix, mix_console, loss_function, init_scale=0.
     several sections is compared with a target profile that was pooled over a whole reference.
 
     ``ref_mix`` is ``(2, M)``, ``(R, 2, M)`` - ``R`` sections of one reference, pooled - or an ``AudioFeatureProfile`` of batch size 1;
-    a tensor is analysed once, before the loop.  ``loss_function`` must offer ``pooled`` (``AudioFeatureLoss``): anything else raises
-    ``TypeError``.  The keywords are ``optimize``'s, ``keep_best``, ``patience``, ``min_delta``, ``poll_every`` and ``callback``
-    included (``view.params`` and ``view.grads`` have ``S`` rows).  The start point is ``optimize``'s.
+    a tensor is analysed once, before the loop.  ``loss_function`` must offer ``pooled`` (``AudioFeatureLoss``,
+    ``MultiResolutionSTFTLoss``): anything else raises ``TypeError``.  A loss without a ``profile`` method (``MultiResolutionSTFTLoss``)
+    is paired: its ``ref_mix`` is ``(S, 2, n)``, cut like the tracks (``take_sections`` with the same starts and length), and goes to
+    ``pooled`` as it is - the ``S`` sections are one item of ``2 S`` rows; any other section count or length is a ``ValueError``
+    before anything touches the device.  The keywords are ``optimize``'s, ``keep_best``, ``patience``, ``min_delta``, ``poll_every``
+    and ``callback`` included (``view.params`` and ``view.grads`` have ``S`` rows).  The start point is ``optimize``'s.
 
     Returns ``optimize``'s tuple with ``mix (S, 2, n)``, the dictionaries at batch ``S`` and the logits in ``optimize``'s shapes
     ``(1, T, 27)``, ``(1, 25)``, ``(1, 26)``, ready for ``render_blocks``.  ``S = 1`` against a profile is ``optimize`` bit for bit."""
@@ -692,8 +751,10 @@ def optimize_sections_batch(tracks, ref_mix, mix_console, loss_function, init_sc
     ``tracks`` is ``(B, S, T, n)``, or ``(S, T, n)`` with ``batch=B`` (the sectioned song is repeated: restarts).  Rows are item-major:
     the console sees row ``b S + s`` for section ``s`` of item ``b``.  ``ref_mix`` is ``(2, M)`` (one reference for every item),
     ``(B, 2, M)``, ``(B, R, 2, M)`` - every item's reference as ``R`` sections, pooled - or an ``AudioFeatureProfile`` of batch size ``B``
-    or 1; a tensor is analysed once, before the loop.  ``loss_function`` must offer ``pooled`` with ``items`` (``AudioFeatureLoss``):
-    anything else raises ``TypeError``.  ``init_scale`` is a number or ``B`` numbers; item ``b`` starts at the ``b``-th successive
+    or 1; a tensor is analysed once, before the loop.  ``loss_function`` must offer ``pooled`` with ``items`` (``AudioFeatureLoss``,
+    ``MultiResolutionSTFTLoss``): anything else raises ``TypeError``.  For a paired loss (no ``profile`` method:
+    ``MultiResolutionSTFTLoss``) ``ref_mix`` is ``(S, 2, n)`` - one reference, cut like the tracks, for every item - or ``(B, S, 2, n)``,
+    flattened item-major like the mix; any other section count or length is a ``ValueError`` before anything touches the device.  ``init_scale`` is a number or ``B`` numbers; item ``b`` starts at the ``b``-th successive
     ``start_point()`` draw, as in ``optimize_batch``, so ``B = 1`` is ``optimize_sections`` and ``S = 1`` is ``optimize_batch`` against a
     profile, both bit for bit.
 

@@ -244,6 +244,26 @@ int mst_mrstft_forward_finish(const mst_mrstft_desc* d, const double* global_tot
 int mst_mrstft_backward(const mst_mrstft_desc* d, const float* pred, const float* target, const void* tables,
                         const float* grad_loss, float* grad_pred, void* workspace, size_t workspace_bytes,
                         void* stream);
+/* Per-item losses (added at ABI v13, additive): the rows are `items` groups of R = rows / items consecutive rows, item-major (item b
+ * owns rows b R .. b R + R - 1: R = 2 for a stereo item, 2 S for an item of S stereo sections), and losses[b] is what
+ * mst_mrstft_forward returns for item b's rows alone - every mean over R rows, the batch-global ratio (sc_per_example = 0) over the
+ * item's rows, no 1 / items anywhere, so neither in a gradient.  The transform launches are those of mst_mrstft_forward; the reduction
+ * behind them folds in a fixed order (an item's rows ascending, then its resolutions ascending), so equal inputs give equal bits, and
+ * items = 1 gives mst_mrstft_forward's bits.  An item's loss and gradient rows depend on that item's rows only (a NaN stays in its
+ * item).  items < 1 or rows % items != 0: hipErrorInvalidValue before any launch.  Descriptor, tables and workspace (size included)
+ * are those of the scalar calls.
+ *   mst_mrstft_forward_items        losses: `items` fp32 on the device; leaves what mst_mrstft_backward_items needs
+ *   mst_mrstft_forward_items_eval   the same values with nothing kept for a backward (as mst_mrstft_forward_eval)
+ *   mst_mrstft_backward_items       grad_losses: `items` fp32 on the device, item b's cotangent reaches item b's rows only (each backward
+ *                                   coefficient times its item's cotangent is one fp32 product, as in mst_mrstft_backward);
+ *                                   grad_pred (rows, n_samples) is overwritten */
+int mst_mrstft_forward_items(const mst_mrstft_desc* d, int32_t items, const float* pred, const float* target, const void* tables,
+                             float* losses, void* workspace, size_t workspace_bytes, void* stream);
+int mst_mrstft_forward_items_eval(const mst_mrstft_desc* d, int32_t items, const float* pred, const float* target, const void* tables,
+                                  float* losses, void* workspace, size_t workspace_bytes, void* stream);
+int mst_mrstft_backward_items(const mst_mrstft_desc* d, int32_t items, const float* pred, const float* target, const void* tables,
+                              const float* grad_losses, float* grad_pred, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * batch_stereo_peak_normalize (reference mst/utils.py:14-29): y = x / clamp(max_{ch,t}|x|, 1e-8)
