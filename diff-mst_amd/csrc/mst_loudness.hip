@@ -13,6 +13,9 @@
 //                 never written); fixed-order wave sums
 //   k_loud_gate   per row, one wave: block energies from the tile parts, block loudness, absolute and relative gate, the two
 //                 gated means and the log10, all in float64
+// mst_loudness_windows adds a fifth for the gated loudness of every window of a song:
+//   k_loud_windows per (window, row), one wave: both gates over the window's complete blocks, from the float64 block energies and
+//                 block loudness k_loud_gate left in the workspace - the song is filtered once, the filter is warm at a window's start
 // The block boundaries are NOT re-derived on the device: the table holds int(T_g * (j * 0.25) * rate) for every j, evaluated on
 // the host in float64 exactly as pyloudnorm writes it (block j = [bound[j], bound[j + 4]), clipped to the signal).
 // Precision: the recursion, its carries and every sum run in FLOAT64 (input and outputs are fp32).  The 38 Hz high pass has a
@@ -285,6 +288,48 @@ __global__ __launch_bounds__(64) void k_loud_gate(const double* __restrict__ par
     if (lane == 0) lufs[row] = (float)(-0.691 + 10.0 * log10(w));
 }
 
+// one gate of one window: loudness of the mean energy of the blocks [first, first + count) that pass it.  The lanes stride over the
+// blocks and both sums are fixed-order, exactly as k_loud_gate forms them (a window of all the blocks is its result bit for bit)
+template <bool kRelative>
+__device__ __forceinline__ double loud_window_gate(const double* __restrict__ z, const double* __restrict__ lj, int channels, int nblocks,
+                                                   int first, int count, double gamma_r, int lane) {
+    const double gch[kLoudMaxCh] = {1.0, 1.0, 1.0, 1.41, 1.41};
+    double sum[kLoudMaxCh], cnt = 0.0;
+#pragma unroll
+    for (int c = 0; c < kLoudMaxCh; ++c) sum[c] = 0.0;
+    for (int i = lane; i < count; i += 64) {
+        const int j = first + i;
+        const double l = lj[j];
+        if (kRelative ? (l > gamma_r && l > -70.0) : (l >= -70.0)) {
+            cnt += 1.0;
+#pragma unroll
+            for (int c = 0; c < kLoudMaxCh; ++c)
+                if (c < channels) sum[c] += z[(int64_t)c * nblocks + j];
+        }
+    }
+    cnt = wave_sum_f64(cnt);
+    double w = 0.0;
+#pragma unroll
+    for (int c = 0; c < kLoudMaxCh; ++c) {
+        const double tot = wave_sum_f64(sum[c]);
+        w += gch[c] * (cnt > 0.0 ? tot / cnt : 0.0);
+    }
+    return -0.691 + 10.0 * log10(w);
+}
+
+// grid (windows, rows), one wave per window.  Reads what k_loud_gate left in zb (block energies and block loudness, float64); window w
+// is the blocks [w * hop, w * hop + wblocks), all of them complete (the host counts only those)
+__global__ __launch_bounds__(64) void k_loud_windows(const double* __restrict__ zb, int channels, int nblocks, int wblocks, int hop,
+                                                     float* __restrict__ window_lufs) {
+    const int lane = threadIdx.x, w = blockIdx.x, row = blockIdx.y, rows = gridDim.y, nw = gridDim.x;
+    const double* z = zb + (int64_t)row * channels * nblocks;
+    const double* lj = zb + (int64_t)rows * channels * nblocks + (int64_t)row * nblocks;
+    const int first = w * hop;
+    const double gamma_r = loud_window_gate<false>(z, lj, channels, nblocks, first, wblocks, 0.0, lane) - 10.0;
+    const double l = loud_window_gate<true>(z, lj, channels, nblocks, first, wblocks, gamma_r, lane);
+    if (lane == 0) window_lufs[(int64_t)row * nw + w] = (float)l;
+}
+
 constexpr int kNormSpan = 256 * 16;  // samples per workgroup
 
 // grid (spans, rows * channels).  y dense (rows, channels, n)
@@ -440,6 +485,39 @@ LoudPlan loud_plan(int32_t rows, int32_t channels, int64_t n, int32_t rate) {
     p.ok = true;
     return p;
 }
+
+// distance of two boundaries when the table is equally spaced (bound[k] == k * bound[1] for every k of the table: 44100, 48000,
+// 22050, 32000, 96000, 88200, 24000 Hz among others), 0 otherwise.  The windowed meter counts complete blocks and places windows
+// with it, so it takes no other rate.
+int loud_even_step(int rate) {
+    if (!loud_rate_ok(rate)) return 0;
+    const double T_g = 0.4, step = 0.25, fs = (double)rate;
+    const int64_t d = (int64_t)(T_g * (1.0 * step) * fs);
+    for (int k = 0; k < kLoudMaxBounds; ++k)
+        if ((int64_t)(T_g * ((double)k * step) * fs) != (int64_t)k * d) return 0;  // loud_host_tables' expression
+    return (int)d;
+}
+
+struct LoudWindowsPlan {
+    bool ok;
+    LoudPlan p;
+    int complete, windows;  // complete gating blocks (bound[j + 4] <= n), windows of them
+    size_t lufs, total;     // byte offset of the whole-signal loudness nobody asked for; workspace bytes
+};
+LoudWindowsPlan loud_windows_plan(int32_t rows, int32_t channels, int64_t n, int32_t rate, int32_t wblocks, int32_t hop) {
+    LoudWindowsPlan q{};
+    const int d = loud_even_step(rate);
+    if (d <= 0 || wblocks < 1 || hop < 1) return q;
+    q.p = loud_plan(rows, channels, n, rate);
+    if (!q.p.ok) return q;
+    q.complete = (int)(n / d) - 3;  // n >= 4 d (loud_plan); never more than p.nblocks, which rounds where this floors
+    if (q.complete < 1 || q.complete > q.p.nblocks || wblocks > q.complete) return q;
+    q.windows = (q.complete - wblocks) / hop + 1;
+    q.lufs = q.p.total;
+    q.total = q.p.total + ((size_t)rows * sizeof(float) + 255) / 256 * 256;
+    q.ok = true;
+    return q;
+}
 }  // namespace
 }  // namespace mst
 
@@ -490,6 +568,34 @@ extern "C" int mst_loudness_integrated(const float* x, int32_t rows, int32_t cha
                        (int)sample_rate, tab, (const double*)excl, (const double*)start, part);
     hipLaunchKernelGGL(k_loud_gate, dim3(rows), dim3(64), 0, stream, (const double*)part, (int)channels, n_samples, p.ntiles,
                        p.nblocks, (int)sample_rate, tab, zb, lufs, block_loudness);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_loudness_num_windows(int64_t n_samples, int32_t sample_rate, int32_t window_blocks, int32_t hop_blocks,
+                                        int32_t* num_windows) {
+    if (!num_windows) return hipErrorInvalidValue;
+    const LoudWindowsPlan q = loud_windows_plan(1, 1, n_samples, sample_rate, window_blocks, hop_blocks);
+    *num_windows = q.ok ? q.windows : 0;
+    return q.ok ? 0 : hipErrorInvalidValue;
+}
+extern "C" size_t mst_loudness_windows_workspace_bytes(int32_t rows, int32_t channels, int64_t n_samples, int32_t sample_rate,
+                                                       int32_t window_blocks, int32_t hop_blocks) {
+    const LoudWindowsPlan q = loud_windows_plan(rows, channels, n_samples, sample_rate, window_blocks, hop_blocks);
+    return q.ok ? q.total : 0;
+}
+extern "C" int mst_loudness_windows(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride,
+                                    int64_t channel_stride, int32_t sample_rate, const void* tables, int32_t window_blocks,
+                                    int32_t hop_blocks, float* window_lufs, float* lufs, void* workspace, size_t workspace_bytes,
+                                    void* stream_) {
+    const LoudWindowsPlan q = loud_windows_plan(rows, channels, n_samples, sample_rate, window_blocks, hop_blocks);
+    if (!q.ok || !window_lufs || !workspace || workspace_bytes < q.total) return hipErrorInvalidValue;
+    // the song is filtered once: the meter's own four launches leave every block's energy and loudness in the workspace
+    float* whole = lufs ? lufs : (float*)((char*)workspace + q.lufs);
+    const int status = mst_loudness_integrated(x, rows, channels, n_samples, row_stride, channel_stride, sample_rate, tables, whole,
+                                               nullptr, workspace, q.p.total, stream_);
+    if (status) return status;
+    hipLaunchKernelGGL(k_loud_windows, dim3((unsigned)q.windows, (unsigned)rows), dim3(64), 0, (hipStream_t)stream_,
+                       (const double*)((char*)workspace + q.p.zb), (int)channels, q.p.nblocks, (int)window_blocks, (int)hop_blocks,
+                       window_lufs);
     return (int)hipGetLastError();
 }
 extern "C" int mst_loudness_normalize(const float* x, float* y, const float* lufs, int32_t rows, int32_t channels,

@@ -586,7 +586,7 @@ extern "C" int mst_logit_adam_step_best_batch(const mst_logit_adam_segment* segm
 }
 
 // ---- one parameter set, several gradient rows: the sections of a song fitted together ----------------------------------------------
-constexpr int kOptMaxSections = 64;
+constexpr int kOptMaxSections = MST_OPT_MAX_SECTIONS;
 extern "C" int mst_logit_adam_init_sections(const mst_logit_adam_segment* segments, int32_t n_segments, int32_t sections, void* state,
                                             void* stream) {
     OptArgs a;

@@ -120,11 +120,13 @@ class CtrlLayer(C.Structure):  # mirrors mst_ctrl_layer and mst_ctrl_layer_grads
 
 OPT_MAX_TERMS = 8  # MST_OPT_MAX_TERMS
 OPT_MAX_ITEMS = 1024  # items of mst_logit_adam_step_batch
-OPT_MAX_SECTIONS = 64  # sections of mst_logit_adam_step_sections
+OPT_MAX_SECTIONS = 64  # MST_OPT_MAX_SECTIONS: sections of mst_logit_adam_step_sections, and of mst_pick_sections
 OPT_MAX_LINK_ROWS = 256  # MST_OPT_MAX_LINK_ROWS: rows of the tied segment of mst_logit_adam_step_linked
 OPT_HEADER_WORDS = 16  # int32 words in front of an item's moments
 OPT_BEST_HEADER_WORDS = 16  # int32 words in front of an item's best logits (mst_logit_adam_step_best)
 AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
+LOUDNESS_MAX_BLOCKS = 4092  # MST_LOUDNESS_MAX_BLOCKS: gating blocks of a signal, windows of mst_pick_sections
+PICK_MAX_TRACKS = 256  # MST_PICK_MAX_TRACKS
 
 
 class LogitAdamSegment(C.Structure):  # mirrors mst_logit_adam_segment
@@ -210,6 +212,11 @@ SIGNATURES = {
                                         C.c_size_t, _S]),
     "mst_loudness_normalize": (STATUS, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float,
                                        _P, _S]),
+    "mst_loudness_num_windows": (STATUS, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "mst_loudness_windows_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "mst_loudness_windows": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                                     _P, _P, C.c_size_t, _S]),
+    "mst_pick_sections": (STATUS, [_P, _P, _P, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _S]),
     "mst_resample_tables_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mst_resample_init_tables": (STATUS, [C.c_int32, C.c_int32, _P, _S]),
     "mst_resample_out_samples": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),

@@ -15,6 +15,9 @@ device inside the same one launch.
 ``optimize_sections`` fits ONE parameter set through several sections of a song pooled into one feature vector, and
 ``optimize_sections_batch`` runs a batch of such fits - restarts, several references - in the launches of one.
 
+``pick_sections`` says where those sections should start: it meters every window of the song once on the device and picks windows in
+which, between them, every track plays (``mst_loudness_windows``, ``mst_pick_sections``).
+
 ``links`` / ``stereo_id`` on all four tie the two mono rows of a stereo stem to one set of logits with a mirrored pan.
 
 PARITY UNPINNED: the script cannot be imported (it imports ``StereoCLAPLoss``, which the reference's ``mst/loss.py`` does not define),
@@ -31,7 +34,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _cabi, _desc, _hip
+from . import _cabi, _desc, _hip, utils
 from .loss import AudioFeatureProfile
 
 
@@ -710,6 +713,92 @@ def take_sections(tracks, starts, length):
         if start < 0 or start + length > tracks.shape[1]:
             raise ValueError(f"the section [{start}, {start + length}) does not lie inside the {tracks.shape[1]} samples of the tracks")
     return torch.stack([tracks[:, start:start + length] for start in starts]).contiguous()
+
+
+class SectionPick(NamedTuple):
+    """What ``pick_sections`` returns.  ``starts`` is a list of Python ints in pick order and ``length`` the section length, both as
+    ``take_sections`` takes them; the rest are device tensors over the ``S = len(starts)`` picked windows: ``active (S, T)`` bool - the
+    tracks that play in each, ``covered (T)`` bool - the tracks that play in any, ``track_lufs (T, S)`` and ``mix_lufs (S)`` - the
+    windowed loudness of the tracks and of their mono sum there."""
+    starts: list
+    length: int
+    active: torch.Tensor
+    covered: torch.Tensor
+    track_lufs: torch.Tensor
+    mix_lufs: torch.Tensor
+
+
+def pick_sections(tracks, length, count, *, sample_rate=44100, hop=None, track_floor_lufs=-48.0, mix_floor_lufs=-48.0, min_gap=None):
+    """Where the sections of a sectioned fit should start: up to ``count`` windows of ``length`` samples of ``tracks (T, N)`` in which,
+    between them, every track plays.  A track that is silent in every section of a fit gets a zero gradient for all of its
+    logits and keeps its start point, which ``render_blocks`` then applies to the whole song.
+
+    The ``T`` tracks and their mono sum ``tracks.sum(0)`` are metered once each (``mst.utils.windowed_loudness``: windows every ``hop``
+    samples, default ``sample_rate / 10``).  A track is active in a window when its loudness there reaches ``track_floor_lufs`` (a number
+    or a ``(T,)`` tensor), a window is eligible when the sum reaches ``mix_floor_lufs`` and some track is active in it, and
+    ``mst_pick_sections`` takes, ``count`` times, the eligible window at least ``min_gap`` samples (default ``length``: no two sections
+    overlap) from every window taken so far that has the most active tracks not yet covered - then the most active tracks, then the
+    loudest sum, then the earliest.  The -48 LUFS defaults are the thresholds the reference's data loader drops a crop at
+    (mst/dataloader.py:39-69, :286-309); they apply to the tracks as they are given, BEFORE any loudness normalisation.  Windows that
+    end after the last sample are not offered.  The call reads the device once, for the picked windows.
+
+    Returns a ``SectionPick``; fewer than ``count`` sections come back as they are, none at all is a ``ValueError``.  Check
+    ``pick.covered`` for tracks that play nowhere above their floor.
+
+        pick = pick_sections(tracks, 131072, 4)
+        sections = take_sections(tracks, pick.starts, pick.length)                      # (S, T, 131072)
+        result = optimize_sections(sections, ref_mix, console, AudioFeatureLoss(weights, 44100))
+        mix = render_blocks(tracks, result[1], result[3], result[5], console)
+    """
+    if not isinstance(tracks, torch.Tensor):
+        raise TypeError(f"tracks must be a (n_tracks, n_samples) tensor, got {type(tracks).__name__}")
+    if tracks.dim() != 2 or not tracks.is_floating_point():
+        raise ValueError(f"tracks must be a floating-point (n_tracks, n_samples) tensor, got {tracks.dtype} {tuple(tracks.shape)}")
+    for name, value in (("length", length), ("count", count)):
+        if isinstance(value, bool) or not isinstance(value, int):
+            raise TypeError(f"{name} must be an int, got {type(value).__name__}")
+    T, N = tracks.shape
+    if not 1 <= T <= _cabi.PICK_MAX_TRACKS:
+        raise ValueError(f"the number of tracks must be 1..{_cabi.PICK_MAX_TRACKS}, got {T}")
+    if not 1 <= count <= _cabi.OPT_MAX_SECTIONS:
+        raise ValueError(f"count must be 1..{_cabi.OPT_MAX_SECTIONS} (what optimize_sections takes), got {count}")
+    _, H, starts = utils.loudness_window_grid(N, length, hop, sample_rate)
+    hop_samples = H * utils._block_step(sample_rate)
+    min_gap = length if min_gap is None else min_gap
+    if isinstance(min_gap, bool) or not isinstance(min_gap, int) or min_gap < 0:
+        raise ValueError(f"min_gap must be a non-negative number of samples, got {min_gap!r}")
+    gap = max(1, -(-min_gap // hop_samples))  # windows: the smallest distance of starts that is min_gap samples or more
+    if isinstance(track_floor_lufs, torch.Tensor):
+        if tuple(track_floor_lufs.shape) != (T,):
+            raise ValueError(f"track_floor_lufs must be a number or a ({T},) tensor, got {tuple(track_floor_lufs.shape)}")
+    else:
+        track_floor_lufs = float(track_floor_lufs)
+    mix_floor_lufs = float(mix_floor_lufs)
+    offered = sum(1 for s in starts if s + length <= N)  # NW, or a few less when length is not a whole number of hops
+    if not offered:
+        raise ValueError(f"a section of {length} samples does not fit into the {N} samples of the tracks")
+    _hip.require_cuda(tracks)
+    dev = tracks.device
+    with torch.no_grad():
+        track_lufs, _ = utils.windowed_loudness(tracks.detach().unsqueeze(1), length, hop, sample_rate)
+        mix_lufs, _ = utils.windowed_loudness(tracks.detach().sum(0).view(1, 1, N), length, hop, sample_rate)
+        track_lufs, mix_lufs = track_lufs[:, :offered].contiguous(), mix_lufs.view(-1)[:offered].contiguous()
+        if isinstance(track_floor_lufs, torch.Tensor):
+            floor = track_floor_lufs.detach().to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            floor = torch.full((T,), track_floor_lufs, dtype=torch.float32, device=dev)
+        windows = torch.empty(count, dtype=torch.int32, device=dev)
+        active = torch.empty(count, T, dtype=torch.uint8, device=dev)
+        covered = torch.empty(T, dtype=torch.uint8, device=dev)
+        with _hip.launch_on(dev) as st:
+            _hip.lib().mst_pick_sections(track_lufs, mix_lufs, floor, mix_floor_lufs, T, offered, count, gap, windows, active, covered, st)
+        picked = [w for w in windows.tolist() if w >= 0]  # the one host read; the -1 entries trail
+        if not picked:
+            raise ValueError(f"no window of {length} samples is eligible: the sum of the tracks stays below {mix_floor_lufs} LUFS or no "
+                             "track reaches its floor")
+        index = windows[:len(picked)].long()
+        return SectionPick([starts[w] for w in picked], length, active[:len(picked)].bool(), covered.bool(),
+                           track_lufs.index_select(1, index), mix_lufs.index_select(0, index))
 
 
 def optimize_sections(tracks, ref_mix, mix_console, loss_function, init_scale=0.001, lr=1e-3, n_iters=100, *, betas=(0.9, 0.999),

@@ -132,6 +132,81 @@ def integrated_loudness(x: torch.Tensor, sample_rate: int = 44100, return_blocks
     return lufs.view(lead)
 
 
+_BLOCK_STEP = {}
+
+
+def _block_step(sample_rate):
+    """Samples between two gating-block boundaries when the meter's table ``int(0.4 * (k * 0.25) * rate)`` is equally spaced over all
+    of its 4096 entries (44100, 48000, 22050, 32000, 96000, 88200, 24000 Hz ...); ``ValueError`` for any other rate."""
+    if isinstance(sample_rate, bool) or sample_rate != int(sample_rate):
+        raise ValueError(f"sample_rate must be a whole number of Hz, got {sample_rate!r}")
+    rate = int(sample_rate)
+    step = _BLOCK_STEP.get(rate)
+    if step is None:
+        step = int(0.4 * (1 * 0.25) * rate)
+        if rate < 20500 or any(int(0.4 * (k * 0.25) * rate) != k * step for k in range(4096)):
+            step = 0
+        _BLOCK_STEP[rate] = step
+    if not step:
+        raise ValueError(f"unsupported sample rate {sample_rate}: the windowed meter needs gating blocks that start every rate / 10 "
+                         "samples exactly (44100, 48000, 22050, 32000, 96000, 88200, 24000 Hz do)")
+    return step
+
+
+def loudness_window_grid(n_samples, length, hop=None, sample_rate=44100):
+    """The host arithmetic of ``windowed_loudness``: ``(window_blocks W, hop_blocks H, starts)`` for a signal of ``n_samples``.  With
+    ``step = rate / 10``: the signal has ``NB = n_samples // step - 3`` complete gating blocks, a window of ``length`` samples holds
+    ``W = floor((length - 0.4 rate) / (0.1 rate)) + 1`` of them, ``hop`` (samples, a multiple of ``step``, default ``step``) is ``H``
+    blocks, there are ``NW = (NB - W) // H + 1`` windows and window ``w`` starts at sample ``int(0.4 * (w H * 0.25) * rate)``, the
+    boundary of its first block.  Everything that cannot be metered is a ``ValueError`` here, before any device call."""
+    step = _block_step(sample_rate)
+    rate = int(sample_rate)
+    n_samples, length = int(n_samples), int(length)
+    if length < 0.4 * rate:
+        raise ValueError(f"a window must hold one gating block: length >= {4 * step} samples at {rate} Hz, got {length}")
+    hop = step if hop is None else hop
+    if isinstance(hop, bool) or hop != int(hop) or int(hop) < step or int(hop) % step:
+        raise ValueError(f"hop must be a positive multiple of rate / 10 = {step} samples, got {hop!r}")
+    if n_samples < 0.4 * rate:
+        raise ValueError("Audio must have length greater than the block size.")
+    W, H, NB = length // step - 3, int(hop) // step, n_samples // step - 3
+    if NB > 4092:
+        raise ValueError(f"{n_samples} samples are {NB} gating blocks; the device meter takes 4092 ({4095 * step} samples) at most")
+    if W > NB:
+        raise ValueError(f"a window of {length} samples does not fit into the {n_samples} samples of the signal")
+    return W, H, [int(0.4 * ((w * H) * 0.25) * rate) for w in range((NB - W) // H + 1)]
+
+
+def windowed_loudness(x: torch.Tensor, length: int, hop=None, sample_rate: int = 44100):
+    """Gated loudness (LUFS) of every window of ``length`` samples of ``x (..., channels, n)``, ``hop`` samples apart (a multiple of
+    ``rate / 10``, which is the default) -> ``(lufs (..., NW) fp32 on the device, starts)`` with ``starts`` the list of the windows'
+    first samples, computed on the host (``loudness_window_grid``).  Nothing is read back from the device.
+
+    The signal is K-weighted ONCE (``mst_loudness_windows``): a window's loudness is BS.1770 gating - absolute gate, relative gate, both
+    within the window - over the complete 0.4 s gating blocks inside ``[start, start + length)``, with the filter warm at its start.
+    That is the loudness of the window as a part of the song; ``integrated_loudness(x[..., start:start + length])`` filters the crop
+    from rest and, unless ``length - 0.4 rate`` is a multiple of ``0.1 rate``, counts one clipped partial block more.
+    ``-inf`` where no block of a window passes the gates.  Forward-only, like the meter."""
+    x3 = _as_rows(x)
+    if x3.shape[1] > 5:
+        raise ValueError("Audio must have five channels or less.")
+    W, H, starts = loudness_window_grid(x3.shape[2], length, hop, sample_rate)
+    _hip.require_cuda(x)
+    _forward_only(x, "windowed_loudness")
+    lib = _hip.lib()
+    rows, chs, n = x3.shape
+    rate, dev = int(sample_rate), x3.device
+    tables = _loudness_tables(dev, rate)
+    nbytes = lib.mst_loudness_windows_workspace_bytes(rows, chs, n, rate, W, H)
+    if nbytes == 0:
+        raise ValueError(f"unsupported loudness call: rows={rows}, channels={chs}, n_samples={n}, sample_rate={sample_rate}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(rows, len(starts), dtype=torch.float32, device=dev)
+    with _hip.launch_on(dev) as st:
+        lib.mst_loudness_windows(x3, rows, chs, n, x3.stride(0), x3.stride(1), rate, tables, W, H, out, None, ws, nbytes, st)
+    return out.view(*x.shape[:-2], len(starts)), starts
+
+
 def loudness_normalize(x: torch.Tensor, target_lufs: float, sample_rate: int = 44100, floor_lufs=None):
     """``y = x * 10^((target_lufs - L) / 20)`` with ``L`` the integrated loudness of every ``(channels, n)`` item of
     ``x (..., channels, n)``, the gain formed on the device.  Returns ``(y, lufs (...), keep (...) bool)``, all on the device;

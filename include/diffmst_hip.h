@@ -306,6 +306,50 @@ int mst_loudness_normalize(const float* x, float* y, const float* lufs, int32_t 
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Windowed loudness (an addition to ABI v13): the gated loudness of every window of a song, from ONE pass of the meter.
+ *   complete block  gating block j is complete when bound[j + 4] <= n_samples; there are NB = floor((n - 0.4 rate) / (0.1 rate)) + 1
+ *                   of them (at most MST_LOUDNESS_MAX_BLOCKS).  The clipped partial last block pyloudnorm appends is not used here.
+ *   window w        the blocks w * hop_blocks .. w * hop_blocks + window_blocks - 1; NW = floor((NB - window_blocks) / hop_blocks) + 1
+ *                   windows.  It covers the samples [bound[w * hop_blocks], bound[w * hop_blocks + window_blocks + 3]).
+ *   its loudness    BS.1770 gating over exactly those blocks, every sum in float64: absolute gate l_j >= -70, Gamma_r from the mean
+ *                   of the survivors minus 10, final set l_j > Gamma_r and l_j > -70, -0.691 + 10 log10(sum_c G_c mean z_c); -inf
+ *                   when the final set is empty.  The block energies are those of the song filtered once - the K-weighting is warm
+ *                   at a window's start: this is the loudness of the window as part of the song, not of the crop filtered from rest.
+ *   window_lufs     (rows, NW) fp32
+ *   lufs            NULL or (rows) fp32: the whole signal's loudness, bit for bit what mst_loudness_integrated writes
+ * The boundary table must be equally spaced, bound[k] == k * bound[1] for every k of the table (44100, 48000, 22050, 32000, 96000,
+ * 88200, 24000 Hz are; 44101 Hz is not).  Any other rate, window_blocks or hop_blocks < 1, window_blocks > NB and whatever
+ * mst_loudness_workspace_bytes refuses is refused: mst_loudness_windows_workspace_bytes returns 0, and mst_loudness_num_windows -
+ * a status like every entry that is not a size - writes 0 windows and returns an error.  num_windows is a host pointer.
+ * x, the strides and the tables are mst_loudness_integrated's.  Its four launches and one more (k_loud_windows, one wave per window
+ * and row, fixed-order sums); deterministic, no host synchronisation, nothing relies on a cleared workspace. */
+#define MST_LOUDNESS_MAX_BLOCKS 4092
+int mst_loudness_num_windows(int64_t n_samples, int32_t sample_rate, int32_t window_blocks, int32_t hop_blocks, int32_t* num_windows);
+size_t mst_loudness_windows_workspace_bytes(int32_t rows, int32_t channels, int64_t n_samples, int32_t sample_rate,
+                                            int32_t window_blocks, int32_t hop_blocks);
+int mst_loudness_windows(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride, int64_t channel_stride,
+                         int32_t sample_rate, const void* tables, int32_t window_blocks, int32_t hop_blocks, float* window_lufs,
+                         float* lufs, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The section picker (csrc/mst_sections.hip): which windows of a song a sectioned fit should see, so that every track plays
+ * in one of them.  One workgroup, deterministic, never waits on the host.
+ *   track_lufs (n_tracks, n_windows) fp32, mix_lufs (n_windows): windowed loudness of the tracks and of their mix
+ *   active[t][w]  = track_lufs[t][w] >= track_floor[t]   (NaN and -inf are not active, by the comparison)
+ *   eligible[w]   = mix_lufs[w] >= mix_floor and some track is active in w
+ *   round r = 0 .. count - 1: the candidates are the eligible w with |w - c| >= min_gap for every window c chosen so far; the one with
+ *   the lexicographically largest (new[w], act[w], mix_lufs[w], -w) is taken - new[w] the number of active tracks not yet covered,
+ *   act[w] the number of active tracks - and its active tracks become covered.  When no candidate is left, this and every later
+ *   entry of `windows` is -1 and its row of `active` zero.
+ *   windows (count) int32; active (count, n_tracks) bytes, row r = active[:, windows[r]]; covered (n_tracks) bytes
+ * n_tracks 1..MST_PICK_MAX_TRACKS, n_windows 1..MST_LOUDNESS_MAX_BLOCKS, count 1..MST_OPT_MAX_SECTIONS (what
+ * mst_logit_adam_step_sections takes), min_gap >= 1: anything else is an error status and no launch. */
+#define MST_PICK_MAX_TRACKS 256
+#define MST_OPT_MAX_SECTIONS 64
+int mst_pick_sections(const float* track_lufs, const float* mix_lufs, const float* track_floor, float mix_floor, int32_t n_tracks,
+                      int32_t n_windows, int32_t count, int32_t min_gap, int32_t* windows, uint8_t* active, uint8_t* covered,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sample-rate conversion (ABI v11) with the semantics of torchaudio.functional.resample(x, orig_freq, new_freq) at its defaults
  * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) - what every script of the reference applies to the tracks and the
  * reference mix before anything else (scripts/run.py:78-79, scripts/online.py:223-226, mst/callbacks/mix.py:52).  PARITY UNPINNED: a
