@@ -16,6 +16,9 @@
 // mst_loudness_windows adds a fifth for the gated loudness of every window of a song:
 //   k_loud_windows per (window, row), one wave: both gates over the window's complete blocks, from the float64 block energies and
 //                 block loudness k_loud_gate left in the workspace - the song is filtered once, the filter is warm at a window's start
+// mst_loudness_range adds a fifth of its own for short-term loudness and the EBU Tech 3342 loudness range:
+//   k_loud_range   per row, one workgroup: the energy of every 3 s window from the tile parts k_loud_run left, both gates, and the two
+//                 percentiles picked by rank - float64, fixed order
 // The block boundaries are NOT re-derived on the device: the table holds int(T_g * (j * 0.25) * rate) for every j, evaluated on
 // the host in float64 exactly as pyloudnorm writes it (block j = [bound[j], bound[j + 4]), clipped to the signal).
 // Precision: the recursion, its carries and every sum run in FLOAT64 (input and outputs are fp32).  The 38 Hz high pass has a
@@ -330,18 +333,96 @@ __global__ __launch_bounds__(64) void k_loud_windows(const double* __restrict__ 
     if (lane == 0) window_lufs[(int64_t)row * nw + w] = (float)l;
 }
 
+constexpr int kRangeWG = 256;
+constexpr int kRangeMax = 4096;  // short-term windows of a signal: at most kLoudMaxBounds - 30 of them
+
+// sum over the workgroup in a fixed order (lane order inside a wave, then wave 0, 1, ...), the same value in every lane
+__device__ __forceinline__ double range_block_sum(double v, double* scratch) {
+    v = wave_sum_f64(v);
+    __syncthreads();  // the last round's readers are done with scratch
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = scratch[0];
+#pragma unroll
+    for (int w = 1; w < kRangeWG / 64; ++w) t += scratch[w];
+    return t;
+}
+__device__ __forceinline__ double loud_of_energy(double e) { return -0.691 + 10.0 * log10(e); }
+
+// grid (rows), after the meter's four launches.  Short-term window k = samples [bound[k hop], bound[k hop + 30]) (3 s); its energy
+// comes from the tile parts k_loud_run left, through the span helper k_loud_gate uses.  EBU Tech 3342: absolute gate l >= -70, relative
+// gate l >= -20 + loudness of the mean energy of the absolutely gated windows, LRA = l(95th) - l(10th percentile) of the survivors.
+// The percentiles are picked by RANK: a survivor's rank is the number of survivors with a smaller energy (or an equal one and a
+// smaller index), which is its place in the ascending sort - exact, no ordering of floating-point sums involved, ties cannot change a
+// value.  Everything in float64; nothing read here was left by an earlier call.
+__global__ __launch_bounds__(kRangeWG) void k_loud_range(const double* __restrict__ part, int channels, int ntiles, int nshort, int hop,
+                                                         int rate, const LoudTables* __restrict__ tab, float* __restrict__ short_term,
+                                                         float* __restrict__ range_lu, float* __restrict__ range_bounds) {
+    __shared__ double e[kRangeMax];  // window energies; -1 once a gate has removed the window
+    __shared__ double scratch[kRangeWG / 64];
+    __shared__ double picked[2];
+    const int tid = threadIdx.x, row = blockIdx.x;
+    const double gch[kLoudMaxCh] = {1.0, 1.0, 1.0, 1.41, 1.41};
+    const double denom = 30.0 * (double)tab->bounds[1];
+    double sum = 0.0, cnt = 0.0;
+    for (int k = tid; k < nshort; k += kRangeWG) {
+        const int64_t lo = tab->bounds[k * hop], hi = tab->bounds[k * hop + 30];
+        double w = 0.0;
+        for (int c = 0; c < channels; ++c)
+            w += gch[c] * (loud_block_sum(part + ((int64_t)row * channels + c) * ntiles * 2, tab->bounds, lo, hi, rate) / denom);
+        const double l = loud_of_energy(w);
+        if (short_term) short_term[(int64_t)row * nshort + k] = (float)l;
+        const bool in = l >= -70.0;
+        e[k] = in ? w : -1.0;
+        if (in) {
+            sum += w;
+            cnt += 1.0;
+        }
+    }
+    sum = range_block_sum(sum, scratch);
+    cnt = range_block_sum(cnt, scratch);
+    const double gamma_r = loud_of_energy(cnt > 0.0 ? sum / cnt : 0.0) - 20.0;
+    double m_ = 0.0;
+    for (int k = tid; k < nshort; k += kRangeWG) {  // every lane re-reads what it wrote itself
+        if (e[k] >= 0.0 && !(loud_of_energy(e[k]) >= gamma_r)) e[k] = -1.0;
+        if (e[k] >= 0.0) m_ += 1.0;
+    }
+    const int m = (int)range_block_sum(m_, scratch);  // (its barriers publish e)
+    if (tid < 2) picked[tid] = 0.0;
+    __syncthreads();
+    const int want_lo = ((m - 1) * 10 + 50) / 100, want_hi = ((m - 1) * 95 + 50) / 100;
+    for (int k = tid; k < nshort; k += kRangeWG) {
+        const double mine = e[k];
+        if (mine < 0.0) continue;
+        int rank = 0;
+        for (int j = 0; j < nshort; ++j) {
+            const double o = e[j];
+            rank += (o >= 0.0 && (o < mine || (o == mine && j < k))) ? 1 : 0;
+        }
+        if (rank == want_lo) picked[0] = mine;  // ranks are a permutation of 0 .. m - 1: one writer each
+        if (rank == want_hi) picked[1] = mine;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double l_lo = loud_of_energy(picked[0]), l_hi = loud_of_energy(picked[1]);
+        range_lu[row] = m > 0 ? (float)(l_hi - l_lo) : 0.0f;
+        if (range_bounds) {
+            range_bounds[row * 2] = m > 0 ? (float)l_lo : __int_as_float(0x7fc00000);
+            range_bounds[row * 2 + 1] = m > 0 ? (float)l_hi : __int_as_float(0x7fc00000);
+        }
+    }
+}
+
 constexpr int kNormSpan = 256 * 16;  // samples per workgroup
 
-// grid (spans, rows * channels).  y dense (rows, channels, n)
-__global__ __launch_bounds__(256) void k_loud_normalize(const float* __restrict__ x, float* __restrict__ y,
-                                                        const float* __restrict__ lufs, int channels, int64_t n,
-                                                        int64_t row_stride, int64_t channel_stride, float target, float floor_lufs,
-                                                        uint8_t* __restrict__ keep) {
-    const int s = blockIdx.y, row = s / channels, tid = threadIdx.x;
-    const float L = lufs[row];
-    const bool kept = L >= floor_lufs && L > -INFINITY && L < INFINITY;  // a silent row (-inf) is dropped whatever the floor
-    const float g = kept ? (float)pow(10.0, ((double)target - (double)L) / 20.0) : 0.0f;
-    if (keep && blockIdx.x == 0 && tid == 0 && s % channels == 0) keep[row] = kept ? 1 : 0;
+__device__ __forceinline__ bool loud_row_kept(float L, float floor_lufs) {
+    return L >= floor_lufs && L > -INFINITY && L < INFINITY;  // a silent row (-inf) is dropped whatever the floor
+}
+
+// one workgroup's span of one signal: y = g x, or zeros for a row that is not kept
+__device__ __forceinline__ void loud_scale_span(const float* __restrict__ x, float* __restrict__ y, int s, int channels, int64_t n,
+                                                int64_t row_stride, int64_t channel_stride, bool kept, float g) {
+    const int tid = threadIdx.x;
     const float* xr = loud_signal(x, s, channels, row_stride, channel_stride);
     float* yr = y + (int64_t)s * n;
     const int64_t base = (int64_t)blockIdx.x * kNormSpan;
@@ -356,6 +437,40 @@ __global__ __launch_bounds__(256) void k_loud_normalize(const float* __restrict_
         }
         store4(yr, i, n, v);
     }
+}
+
+// grid (spans, rows * channels).  y dense (rows, channels, n)
+__global__ __launch_bounds__(256) void k_loud_normalize(const float* __restrict__ x, float* __restrict__ y,
+                                                        const float* __restrict__ lufs, int channels, int64_t n,
+                                                        int64_t row_stride, int64_t channel_stride, float target, float floor_lufs,
+                                                        uint8_t* __restrict__ keep) {
+    const int s = blockIdx.y, row = s / channels, tid = threadIdx.x;
+    const float L = lufs[row];
+    const bool kept = loud_row_kept(L, floor_lufs);
+    const float g = kept ? (float)pow(10.0, ((double)target - (double)L) / 20.0) : 0.0f;
+    if (keep && blockIdx.x == 0 && tid == 0 && s % channels == 0) keep[row] = kept ? 1 : 0;
+    loud_scale_span(x, y, s, channels, n, row_stride, channel_stride, kept, g);
+}
+
+// the same with the gain capped so that the true peak stays at or below `ceiling` dBTP: g = min(10^((target - L) / 20),
+// 10^(ceiling / 20) / TP), TP the linear true peak of the row (mst_true_peak).  gain_db (rows): what was applied, -inf for a dropped row
+__global__ __launch_bounds__(256) void k_loud_normalize_limited(const float* __restrict__ x, float* __restrict__ y,
+                                                                const float* __restrict__ lufs, const float* __restrict__ true_peak,
+                                                                int channels, int64_t n, int64_t row_stride, int64_t channel_stride,
+                                                                float target, float floor_lufs, float ceiling,
+                                                                float* __restrict__ gain_db, uint8_t* __restrict__ keep) {
+    const int s = blockIdx.y, row = s / channels, tid = threadIdx.x;
+    const float L = lufs[row], tp = true_peak[row];
+    const bool kept = loud_row_kept(L, floor_lufs);
+    const double g_loud = pow(10.0, ((double)target - (double)L) / 20.0), g_peak = pow(10.0, (double)ceiling / 20.0) / (double)tp;
+    const bool capped = tp > 0.0f && g_peak < g_loud;
+    const float g = kept ? (float)(capped ? g_peak : g_loud) : 0.0f;
+    if (blockIdx.x == 0 && tid == 0 && s % channels == 0) {
+        if (keep) keep[row] = kept ? 1 : 0;
+        const double db = capped ? (double)ceiling - 20.0 * log10((double)tp) : (double)target - (double)L;
+        gain_db[row] = kept ? (float)db : -INFINITY;
+    }
+    loud_scale_span(x, y, s, channels, n, row_stride, channel_stride, kept, g);
 }
 
 // the table travels to the device as kernel arguments (no host buffer has to outlive the call, nothing is cached in the library)
@@ -518,6 +633,29 @@ LoudWindowsPlan loud_windows_plan(int32_t rows, int32_t channels, int64_t n, int
     q.ok = true;
     return q;
 }
+
+// short-term windows of 30 segments of step = rate / 10 samples, hop segments apart: the equally spaced table again
+struct LoudRangePlan {
+    bool ok;
+    LoudPlan p;
+    int nshort;
+    size_t lufs, total;  // as LoudWindowsPlan
+};
+LoudRangePlan loud_range_plan(int32_t rows, int32_t channels, int64_t n, int32_t rate, int32_t hop) {
+    LoudRangePlan q{};
+    const int d = loud_even_step(rate);
+    if (d <= 0 || hop < 1 || hop > 30) return q;
+    q.p = loud_plan(rows, channels, n, rate);
+    if (!q.p.ok) return q;
+    const int64_t nseg = n / d;  // at most kLoudMaxBounds - 1 (loud_plan: n / d - 3 <= nblocks <= 4092)
+    if (nseg < 30 || nseg > kLoudMaxBounds - 1) return q;
+    q.nshort = (int)((nseg - 30) / hop + 1);
+    if (q.nshort > kRangeMax) return q;
+    q.lufs = q.p.total;
+    q.total = q.p.total + ((size_t)rows * sizeof(float) + 255) / 256 * 256;
+    q.ok = true;
+    return q;
+}
 }  // namespace
 }  // namespace mst
 
@@ -596,6 +734,48 @@ extern "C" int mst_loudness_windows(const float* x, int32_t rows, int32_t channe
     hipLaunchKernelGGL(k_loud_windows, dim3((unsigned)q.windows, (unsigned)rows), dim3(64), 0, (hipStream_t)stream_,
                        (const double*)((char*)workspace + q.p.zb), (int)channels, q.p.nblocks, (int)window_blocks, (int)hop_blocks,
                        window_lufs);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_loudness_num_short_term(int64_t n_samples, int32_t sample_rate, int32_t hop_segments, int32_t* count) {
+    if (!count) return hipErrorInvalidValue;
+    const LoudRangePlan q = loud_range_plan(1, 1, n_samples, sample_rate, hop_segments);
+    *count = q.ok ? q.nshort : 0;
+    return q.ok ? 0 : hipErrorInvalidValue;
+}
+extern "C" size_t mst_loudness_range_workspace_bytes(int32_t rows, int32_t channels, int64_t n_samples, int32_t sample_rate,
+                                                     int32_t hop_segments) {
+    const LoudRangePlan q = loud_range_plan(rows, channels, n_samples, sample_rate, hop_segments);
+    return q.ok ? q.total : 0;
+}
+extern "C" int mst_loudness_range(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride,
+                                  int64_t channel_stride, int32_t sample_rate, const void* tables, int32_t hop_segments,
+                                  float* short_term_lufs, float* range_lu, float* range_bounds, float* lufs, float* block_loudness,
+                                  void* workspace, size_t workspace_bytes, void* stream_) {
+    const LoudRangePlan q = loud_range_plan(rows, channels, n_samples, sample_rate, hop_segments);
+    if (!q.ok || !range_lu || !workspace || workspace_bytes < q.total) return hipErrorInvalidValue;
+    // one K-weighting pass: the meter's own four launches, which also write lufs and block_loudness exactly as they always do
+    float* whole = lufs ? lufs : (float*)((char*)workspace + q.lufs);
+    const int status = mst_loudness_integrated(x, rows, channels, n_samples, row_stride, channel_stride, sample_rate, tables, whole,
+                                               block_loudness, workspace, q.p.total, stream_);
+    if (status) return status;
+    hipLaunchKernelGGL(k_loud_range, dim3((unsigned)rows), dim3(kRangeWG), 0, (hipStream_t)stream_,
+                       (const double*)((char*)workspace + q.p.part), (int)channels, q.p.ntiles, q.nshort, (int)hop_segments,
+                       (int)sample_rate, (const LoudTables*)tables, short_term_lufs, range_lu, range_bounds);
+    return (int)hipGetLastError();
+}
+extern "C" int mst_loudness_normalize_limited(const float* x, float* y, const float* lufs, const float* true_peak, int32_t rows,
+                                              int32_t channels, int64_t n_samples, int64_t row_stride, int64_t channel_stride,
+                                              float target_lufs, float floor_lufs, float ceiling_dbtp, float* gain_db, uint8_t* keep,
+                                              void* stream_) {
+    if (!x || !y || !lufs || !true_peak || !gain_db || rows <= 0 || channels < 1 || channels > kLoudMaxCh ||
+        (int64_t)rows * channels > 65535 || n_samples <= 0 || row_stride < 0 || channel_stride < 0 || !(target_lufs == target_lufs) ||
+        floor_lufs != floor_lufs || !(ceiling_dbtp == ceiling_dbtp))
+        return hipErrorInvalidValue;
+    const int64_t nblk = (n_samples + kNormSpan - 1) / kNormSpan;
+    if (nblk > 2147483647) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_loud_normalize_limited, dim3((unsigned)nblk, (unsigned)(rows * channels)), dim3(256), 0, (hipStream_t)stream_,
+                       x, y, lufs, true_peak, (int)channels, n_samples, row_stride, channel_stride, target_lufs, floor_lufs, ceiling_dbtp,
+                       gain_db, keep);
     return (int)hipGetLastError();
 }
 extern "C" int mst_loudness_normalize(const float* x, float* y, const float* lufs, int32_t rows, int32_t channels,

@@ -127,6 +127,7 @@ OPT_BEST_HEADER_WORDS = 16  # int32 words in front of an item's best logits (mst
 AF_PROFILE_DOUBLES = 54  # MST_AF_PROFILE_DOUBLES
 LOUDNESS_MAX_BLOCKS = 4092  # MST_LOUDNESS_MAX_BLOCKS: gating blocks of a signal, windows of mst_pick_sections
 PICK_MAX_TRACKS = 256  # MST_PICK_MAX_TRACKS
+TRUE_PEAK_TILE = 2048  # MST_TRUE_PEAK_TILE: positions one workgroup of k_true_peak covers
 
 
 class LogitAdamSegment(C.Structure):  # mirrors mst_logit_adam_segment
@@ -216,6 +217,18 @@ SIGNATURES = {
     "mst_loudness_windows_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "mst_loudness_windows": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P,
                                      _P, _P, C.c_size_t, _S]),
+    "mst_true_peak_factor": (STATUS, [C.c_int32, C.POINTER(C.c_int32)]),
+    "mst_true_peak_coefficients": (STATUS, [C.c_int32, C.POINTER(C.c_float)]),
+    "mst_true_peak_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "mst_true_peak": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t, _S]),
+    "mst_true_peak_sample": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_size_t,
+                                     _S]),
+    "mst_loudness_num_short_term": (STATUS, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "mst_loudness_range_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "mst_loudness_range": (STATUS, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, _P, _P,
+                                   _P, _P, C.c_size_t, _S]),
+    "mst_loudness_normalize_limited": (STATUS, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                                               C.c_float, C.c_float, _P, _P, _S]),
     "mst_pick_sections": (STATUS, [_P, _P, _P, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _S]),
     "mst_resample_tables_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mst_resample_init_tables": (STATUS, [C.c_int32, C.c_int32, _P, _S]),

@@ -1,6 +1,8 @@
 """``mst.utils`` - the helper on the hot path (reference mst/utils.py:14-29)."""
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -231,6 +233,193 @@ def _apply_loudness_gain(x3, lufs, target_lufs, floor_lufs):
     with _hip.launch_on(dev) as st:
         lib.mst_loudness_normalize(x3, y, lufs, rows, chs, n, x3.stride(0), x3.stride(1), float(target_lufs), floor, keep, st)
     return y, keep.bool()
+
+
+# ------------------------------------------------------------------------------------------------
+# The rest of a delivery meter (mst_truepeak.hip, k_loud_range): true peak, short-term and momentary loudness, loudness
+# range, and a normalisation that respects a true-peak ceiling.  PARITY UNPINNED: written from BS.1770-4 Annex 2 and EBU Tech
+# 3341 / 3342, never run against another meter.  All forward-only, nothing is read back from the device.
+# ------------------------------------------------------------------------------------------------
+def true_peak_factor(sample_rate):
+    """Oversampling factor of the true-peak meter: 4 below 96000 Hz, 2 below 192000 Hz; ``ValueError`` for any other rate."""
+    if isinstance(sample_rate, bool) or sample_rate != int(sample_rate) or int(sample_rate) <= 0:
+        raise ValueError(f"sample_rate must be a positive whole number of Hz, got {sample_rate!r}")
+    rate = int(sample_rate)
+    if rate >= 192000:
+        raise ValueError(f"unsupported sample rate {sample_rate}: the true-peak meter oversamples rates below 192000 Hz only")
+    return 4 if rate < 96000 else 2
+
+
+def _true_peak_linear(x3, sample_rate, per_channel=False, sample_peak=False):
+    """``(rows, channels, n)`` -> (true peak (rows), per channel (rows, channels) or None, sample peak max |x| (rows) or None), LINEAR
+    fp32 on the device, all from one pass."""
+    factor = true_peak_factor(sample_rate)
+    lib = _hip.lib()
+    rows, chs, n = x3.shape
+    dev = x3.device
+    nbytes = lib.mst_true_peak_workspace_bytes(rows, chs, n, factor)
+    if nbytes == 0:
+        raise ValueError(f"unsupported true-peak call: rows={rows}, channels={chs}, n_samples={n}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    peak = torch.empty(rows, dtype=torch.float32, device=dev)
+    chan = torch.empty(rows, chs, dtype=torch.float32, device=dev) if per_channel else None
+    sample = torch.empty(rows, dtype=torch.float32, device=dev) if sample_peak else None
+    with _hip.launch_on(dev) as st:
+        lib.mst_true_peak_sample(x3, rows, chs, n, x3.stride(0), x3.stride(1), factor, peak, chan, sample, ws, nbytes, st)
+    return peak, chan, sample
+
+
+def _check_true_peak(x3, sample_rate):
+    true_peak_factor(sample_rate)
+    if x3.shape[2] < 1 or x3.shape[0] * x3.shape[1] < 1:
+        raise ValueError("true_peak needs at least one sample of at least one channel")
+    if x3.shape[0] * x3.shape[1] > 65535:
+        raise ValueError("true_peak takes 65535 signals (items x channels) per call at most")
+
+
+def true_peak(x: torch.Tensor, sample_rate: int = 44100, per_channel: bool = False):
+    """True peak (dBTP, BS.1770-4 Annex 2) of every ``(channels, n)`` item of ``x (..., channels, n)`` -> ``(...)``, or
+    ``(..., channels)`` with ``per_channel``: ``20 log10`` of the largest magnitude of the signal interpolated 4 times (2 times from
+    96 kHz) by a 49-tap Hann-windowed sinc, the tail after the last sample included.  ``-inf`` for silence, NaN for an item that holds
+    a NaN.  The interpolated signal is never written; a last-dimension crop is read in place."""
+    if x.dim() >= 2 and x.numel() == 0:
+        raise ValueError("true_peak needs at least one sample of at least one channel")
+    x3 = _as_rows(x)
+    _check_true_peak(x3, sample_rate)
+    _hip.require_cuda(x)
+    _forward_only(x, "true_peak")
+    peak, chan, _ = _true_peak_linear(x3, sample_rate, per_channel)
+    if per_channel:
+        return (20.0 * torch.log10(chan)).view(*x.shape[:-1])
+    return (20.0 * torch.log10(peak)).view(x.shape[:-2])
+
+
+def short_term_grid(n_samples, hop=None, sample_rate=44100):
+    """The host arithmetic of ``short_term_loudness``: ``(hop_segments H, starts)``.  With ``step = rate / 10`` the signal has
+    ``NSEG = n_samples // step`` segments, a short-term window is 30 of them (3 s), ``hop`` (samples, a multiple of ``step`` of at
+    most 30, default ``10 step`` = 1 s) is ``H`` segments and there are ``(NSEG - 30) // H + 1`` windows, window ``k`` starting at sample
+    ``k H step``.  Everything that cannot be metered is a ``ValueError`` here, before any device call."""
+    step = _block_step(sample_rate)
+    n_samples = int(n_samples)
+    hop = 10 * step if hop is None else hop
+    if isinstance(hop, bool) or hop != int(hop) or int(hop) < step or int(hop) % step or int(hop) > 30 * step:
+        raise ValueError(f"hop must be a multiple of rate / 10 = {step} samples between {step} and {30 * step}, got {hop!r}")
+    nseg = n_samples // step
+    if nseg < 30:
+        raise ValueError(f"short-term loudness needs 3 s of audio ({30 * step} samples at {int(sample_rate)} Hz), got {n_samples}")
+    if nseg - 3 > 4092:
+        raise ValueError(f"{n_samples} samples are {nseg - 3} gating blocks; the device meter takes 4092 ({4095 * step} samples) at most")
+    H = int(hop) // step
+    return H, [k * H * step for k in range((nseg - 30) // H + 1)]
+
+
+def _range_call(x3, sample_rate, H, ns, want_short, want_bounds, want_blocks):
+    """One K-weighting pass and the range launch -> (range (rows), short-term (rows, NS) | None, bounds (rows, 2) | None,
+    lufs (rows), block loudness (rows, NB) | None)."""
+    lib = _hip.lib()
+    rows, chs, n = x3.shape
+    rate, dev = int(sample_rate), x3.device
+    tables = _loudness_tables(dev, rate)
+    nbytes = lib.mst_loudness_range_workspace_bytes(rows, chs, n, rate, H)
+    nblocks = lib.mst_loudness_num_blocks(n, rate)
+    if nbytes == 0 or nblocks == 0:
+        raise ValueError(f"unsupported loudness call: rows={rows}, channels={chs}, n_samples={n}, sample_rate={sample_rate}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lra, lufs = torch.empty(rows, **f32), torch.empty(rows, **f32)
+    short = torch.empty(rows, ns, **f32) if want_short else None
+    bounds = torch.empty(rows, 2, **f32) if want_bounds else None
+    blocks = torch.empty(rows, nblocks, **f32) if want_blocks else None
+    with _hip.launch_on(dev) as st:
+        lib.mst_loudness_range(x3, rows, chs, n, x3.stride(0), x3.stride(1), rate, tables, H, short, lra, bounds, lufs, blocks, ws,
+                               nbytes, st)
+    return lra, short, bounds, lufs, blocks
+
+
+def _range_rows(x, hop, sample_rate, what):
+    x3 = _as_rows(x)
+    if x3.shape[1] > 5:
+        raise ValueError("Audio must have five channels or less.")
+    H, starts = short_term_grid(x3.shape[2], hop, sample_rate)
+    _hip.require_cuda(x)
+    _forward_only(x, what)
+    return x3, H, starts
+
+
+def short_term_loudness(x: torch.Tensor, hop=None, sample_rate: int = 44100):
+    """Short-term loudness (LUFS, ungated, 3 s windows) of ``x (..., channels, n)`` -> ``(lufs (..., NS) on the device, starts)``;
+    ``hop`` in samples, a multiple of ``rate / 10`` (default one second), ``starts`` the windows' first samples (``short_term_grid``).
+    The song is K-weighted once and the filter is warm at a window's start; ``-inf`` for a silent window."""
+    x3, H, starts = _range_rows(x, hop, sample_rate, "short_term_loudness")
+    _, short, _, _, _ = _range_call(x3, sample_rate, H, len(starts), True, False, False)
+    return short.view(*x.shape[:-2], len(starts)), starts
+
+
+def momentary_loudness(x: torch.Tensor, sample_rate: int = 44100):
+    """Momentary loudness (LUFS, ungated, 0.4 s windows every 0.1 s) of ``x (..., channels, n)`` -> ``(..., num_blocks)``: the block
+    loudness the meter already forms (``integrated_loudness(x, rate, return_blocks=True)[1]``)."""
+    return integrated_loudness(x, sample_rate, return_blocks=True)[1]
+
+
+def loudness_range(x: torch.Tensor, sample_rate: int = 44100, hop=None, return_bounds: bool = False):
+    """Loudness range (LU, EBU Tech 3342) of every item of ``x (..., channels, n)`` -> ``(...)``: the spread between the 10th and the
+    95th percentile of the short-term loudness that passes an absolute gate at -70 LUFS and a relative gate 20 LU below the gated
+    mean.  With ``return_bounds`` also ``(..., 2)``, the two percentiles in LUFS (NaN where no window survives; the range is 0
+    there).  ``hop`` as in ``short_term_loudness``; Tech 3342 asks for at least 2 s of overlap, i.e. ``hop <= rate``."""
+    x3, H, starts = _range_rows(x, hop, sample_rate, "loudness_range")
+    lra, _, bounds, _, _ = _range_call(x3, sample_rate, H, len(starts), False, return_bounds, False)
+    lead = x.shape[:-2]
+    return (lra.view(lead), bounds.view(*lead, 2)) if return_bounds else lra.view(lead)
+
+
+class LoudnessReport(NamedTuple):
+    """What a delivery meter shows, every field a device tensor of the input's leading shape: LUFS, LU, LUFS, LUFS, dBTP, dBFS."""
+    integrated: torch.Tensor
+    loudness_range: torch.Tensor
+    momentary_max: torch.Tensor
+    short_term_max: torch.Tensor
+    true_peak: torch.Tensor
+    sample_peak: torch.Tensor
+
+
+def meter_report(x: torch.Tensor, sample_rate: int = 44100) -> LoudnessReport:
+    """The meter readings of every item of ``x (..., channels, n)`` from one K-weighting pass, one range launch (short-term hop of one
+    second) and the true-peak launches; the maxima are ``amax`` of the momentary and short-term series."""
+    x3, H, starts = _range_rows(x, None, sample_rate, "meter_report")
+    _check_true_peak(x3, sample_rate)
+    lra, short, _, lufs, blocks = _range_call(x3, sample_rate, H, len(starts), True, False, True)
+    peak, _, sample = _true_peak_linear(x3, sample_rate, sample_peak=True)
+    lead = x.shape[:-2]
+    sample = 20.0 * torch.log10(sample)
+    return LoudnessReport(lufs.view(lead), lra.view(lead), blocks.amax(dim=1).view(lead), short.amax(dim=1).view(lead),
+                          (20.0 * torch.log10(peak)).view(lead), sample.view(lead))
+
+
+def loudness_normalize_limited(x: torch.Tensor, target_lufs: float, ceiling_dbtp: float = -1.0, sample_rate: int = 44100,
+                               floor_lufs=None):
+    """``loudness_normalize`` with the gain capped so that the true peak of the result stays at or below ``ceiling_dbtp``:
+    ``g = min(10^((target_lufs - L) / 20), 10^(ceiling_dbtp / 20) / TP)``, formed on the device.  Returns ``(y, lufs (...), keep (...)
+    bool, gain_db (...), true_peak (...) dBTP of the input)``; an item the cap took hold of ends ``target - L - gain_db`` LU below
+    the target.  Items below ``floor_lufs`` and silent ones have ``keep = False``, come back as zeros and have ``gain_db = -inf``."""
+    x3 = _as_rows(x)
+    _check_audio(x3.shape[1], x3.shape[2], sample_rate)
+    _check_true_peak(x3, sample_rate)
+    _hip.require_cuda(x)
+    _forward_only(x, "loudness_normalize_limited")
+    lufs, _ = _meter(x3, sample_rate, False)
+    peak, _, _ = _true_peak_linear(x3, sample_rate)
+    lib = _hip.lib()
+    rows, chs, n = x3.shape
+    dev = x3.device
+    y = torch.empty(rows, chs, n, dtype=torch.float32, device=dev)
+    keep = torch.empty(rows, dtype=torch.uint8, device=dev)
+    gain = torch.empty(rows, dtype=torch.float32, device=dev)
+    floor = float("-inf") if floor_lufs is None else float(floor_lufs)
+    with _hip.launch_on(dev) as st:
+        lib.mst_loudness_normalize_limited(x3, y, lufs, peak, rows, chs, n, x3.stride(0), x3.stride(1), float(target_lufs), floor,
+                                           float(ceiling_dbtp), gain, keep, st)
+    lead = x.shape[:-2]
+    return y.view(x.shape), lufs.view(lead), keep.bool().view(lead), gain.view(lead), (20.0 * torch.log10(peak)).view(lead)
 
 
 class LoudnessMeter:

@@ -331,6 +331,61 @@ int mst_loudness_windows(const float* x, int32_t rows, int32_t channels, int64_t
                          int32_t sample_rate, const void* tables, int32_t window_blocks, int32_t hop_blocks, float* window_lufs,
                          float* lufs, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The rest of a delivery meter (additions to ABI v13): true peak, short-term loudness, loudness range, and a normalisation
+ * that respects a true-peak ceiling.  PARITY UNPINNED: written from the published definitions (BS.1770-4 Annex 2, EBU Tech 3341 /
+ * 3342, libebur128's interpolator), never run against another meter.
+ *
+ * True peak of an item x (channels, n), oversampling factor F = 4 below 96000 Hz, 2 from 96000 Hz to below 192000 Hz (anything else is
+ * refused: mst_true_peak_factor - a status like every entry that is not a size - writes 0 and returns an error; factor is a host pointer):
+ *   h[j] = sinc((j - 24) / F) * 0.5 * (1 - cos(2 pi j / 48)), j = 0..48, float64 on the host, rounded once to fp32; the sinc is exact
+ *          at whole arguments, so phase 0 is the identity (h[24] = 1, exact zeros) and the sample peak is always contained.
+ *          mst_true_peak_coefficients (host only) returns the 49 fp32 taps the kernel uses.
+ *   y[k] = sum_j h[j] xz[(k - j) / F] over the j with (k - j) % F == 0, xz = x extended by zeros, k = 0 .. F (n - 1) + 48: the FULL
+ *          convolution - the samples after the last input count, which libebur128 (it never flushes its delay line) leaves out; the
+ *          result does not depend on where the signal sits in a buffer.
+ *   TP   = max over channels and k of |y|, fp32 fused multiply-adds in a fixed tap order (at F = 2 two halves of 12 taps, added).
+ *          Silence gives 0, a NaN in an item makes that item's result NaN (and no other's), an infinity gives +inf.
+ *   true_peak (rows) LINEAR fp32 (20 log10 of it is dBTP); channel_peak NULL or (rows, channels).
+ * x: unit sample stride, row_stride / channel_stride elements, any 4-byte alignment.  rows * channels <= 65535, n_samples >= 1.  Two
+ * launches (one workgroup per MST_TRUE_PEAK_TILE positions and signal, then one wave per row), no atomics, deterministic; the
+ * interpolated signal is never written; nothing relies on a cleared workspace. */
+#define MST_TRUE_PEAK_TILE 2048
+int mst_true_peak_factor(int32_t sample_rate, int32_t* factor);
+int mst_true_peak_coefficients(int32_t factor, float* h49);
+size_t mst_true_peak_workspace_bytes(int32_t rows, int32_t channels, int64_t n_samples, int32_t factor);
+int mst_true_peak(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride, int64_t channel_stride,
+                  int32_t factor, float* true_peak, float* channel_peak, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two launches, also writing sample_peak NULL | (rows) linear fp32: max |x| over the item, which is phase 0 of the interpolator
+ * and falls out of the same pass (a meter report shows it beside the true peak).  NaN rule as above; same workspace. */
+int mst_true_peak_sample(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride, int64_t channel_stride,
+                         int32_t factor, float* true_peak, float* channel_peak, float* sample_peak, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* Short-term loudness and loudness range (EBU Tech 3342), from the meter's ONE K-weighting pass.  With step = rate / 10 (the equally
+ * spaced boundary table mst_loudness_windows needs; other rates are refused) a signal has NSEG = n / step complete segments:
+ *   short-term window k  the samples [bound[k H], bound[k H + 30]) = 3 s, H = hop_segments in 1..30; NS = (NSEG - 30) / H + 1 windows;
+ *                        E_k = sum_c G_c (sum of the K-weighted y^2 over the window) / (30 step), l_k = -0.691 + 10 log10 E_k, ungated
+ *   range                absolute gate l_k >= -70; relative gate l_k >= -20 + loudness of the mean E_k of the absolutely gated windows;
+ *                        the m survivors in ascending order of energy: lo = element ((m - 1) * 10 + 50) / 100, hi = element
+ *                        ((m - 1) * 95 + 50) / 100 (integers); LRA = l(hi) - l(lo), 0 when m == 0.  All in float64, fixed order.
+ *   short_term_lufs NULL or (rows, NS); range_lu (rows); range_bounds NULL or (rows, 2) = l(lo), l(hi) (NaN when m == 0);
+ *   lufs NULL or (rows) and block_loudness NULL or (rows, num_blocks): bit for bit what mst_loudness_integrated writes.
+ * A signal shorter than 3 s, H outside 1..30 and whatever mst_loudness_workspace_bytes refuses are refused
+ * (mst_loudness_range_workspace_bytes returns 0; mst_loudness_num_short_term writes 0 through its host pointer and returns an error).
+ * The meter's four launches and one more (k_loud_range, one workgroup per row). */
+int mst_loudness_num_short_term(int64_t n_samples, int32_t sample_rate, int32_t hop_segments, int32_t* count);
+size_t mst_loudness_range_workspace_bytes(int32_t rows, int32_t channels, int64_t n_samples, int32_t sample_rate, int32_t hop_segments);
+int mst_loudness_range(const float* x, int32_t rows, int32_t channels, int64_t n_samples, int64_t row_stride, int64_t channel_stride,
+                       int32_t sample_rate, const void* tables, int32_t hop_segments, float* short_term_lufs, float* range_lu,
+                       float* range_bounds, float* lufs, float* block_loudness, void* workspace, size_t workspace_bytes, void* stream);
+/* mst_loudness_normalize with the gain capped at a true-peak ceiling: g = min(10^((target_lufs - lufs[row]) / 20),
+ * 10^(ceiling_dbtp / 20) / true_peak[row]), formed on the device from the two buffers (true_peak LINEAR, as mst_true_peak writes it).
+ * gain_db (rows): the gain that was applied, ceiling_dbtp - 20 log10(true_peak) where the cap took hold, target_lufs - lufs elsewhere,
+ * -inf for a row that is not kept.  keep and the zero rows are mst_loudness_normalize's. */
+int mst_loudness_normalize_limited(const float* x, float* y, const float* lufs, const float* true_peak, int32_t rows, int32_t channels,
+                                   int64_t n_samples, int64_t row_stride, int64_t channel_stride, float target_lufs, float floor_lufs,
+                                   float ceiling_dbtp, float* gain_db, uint8_t* keep, void* stream);
+
 /* The section picker (csrc/mst_sections.hip): which windows of a song a sectioned fit should see, so that every track plays
  * in one of them.  One workgroup, deterministic, never waits on the host.
  *   track_lufs (n_tracks, n_windows) fp32, mix_lufs (n_windows): windowed loudness of the tracks and of their mix
