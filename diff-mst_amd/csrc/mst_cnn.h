@@ -45,4 +45,19 @@ void launch_conv_wgrad(int precision, const WgradArgs& a, hipStream_t s);
 bool conv_wgrad_nine_taps(int precision, int W, int Cin, int Cout);
 int conv_pixel_tiles(int N, int H, int W);
 
+// One convolution at a time (mst_cnn_net.hip): the bodies of the C ABI's mst_conv3x3_* / mst_conv_wgrad* entries, argument for argument
+// (include/diffmst_hip.h).  Weak: mst_conv_seam.hip, which exports the entries, is also linked into libraries that leave the encoder's
+// matrix-core kernels out (the host simulator); there the references are null and the entries report sizes of 0 / hipErrorNotSupported.
+#define MST_SEAM_WEAK __attribute__((weak))
+MST_SEAM_WEAK size_t seam_conv3x3_workspace_bytes(int32_t precision, int32_t cin, int32_t cout);
+MST_SEAM_WEAK size_t seam_conv3x3_splitk_bytes(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dgrad);
+MST_SEAM_WEAK size_t seam_conv3x3_part_bytes(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dgrad);
+MST_SEAM_WEAK int seam_conv3x3(int32_t precision, int32_t dgrad, const void* x, const float* weight, void* out, float* part, int32_t* tiles,
+                               int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, void* workspace, size_t workspace_bytes, void* splitk,
+                               size_t splitk_bytes, void* stream);
+MST_SEAM_WEAK size_t seam_conv_wgrad_workspace_bytes(int32_t precision, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout);
+MST_SEAM_WEAK int seam_conv_wgrad(int32_t precision, const void* dy, const void* x, float* grad_weight, int32_t n, int32_t h, int32_t w,
+                                  int32_t cin, int32_t cout, void* workspace, size_t workspace_bytes, int32_t* splits, int32_t* steps_per_split,
+                                  void* stream);
+
 }  // namespace mst

@@ -909,3 +909,87 @@ extern "C" int mst_cnn14_backward_sync(const mst_cnn14_desc* d, const float* spe
     if (d->precision == 0) return cnn_backward_t<bf16_t>(d, p, spec, params, grad_embed, grads, (char*)workspace, (hipStream_t)stream, sync, user);
     return cnn_backward_t<float>(d, p, spec, params, grad_embed, grads, (char*)workspace, (hipStream_t)stream, sync, user);
 }
+
+// =====================================================================================================================
+// One convolution at a time (mst_conv_seam.hip exports these as mst_conv3x3 / mst_conv_wgrad; tests/test_conv_routes_gpu.py): the launch
+// sequence the network runs for ONE layer - weight preparation, launcher, fold - with nothing of the network around it.  No kernel and
+// no dispatch rule lives here.
+static bool conv_seam_shape(int precision, int n, int h, int w, int cin, int cout) {
+    auto chan = [](int c) { return c >= 64 && c <= 2048 && (c & (c - 1)) == 0; };
+    if (precision < 0 || precision > 3 || n <= 0 || h <= 0 || w <= 0 || (int64_t)n * h * w > (1ll << 26)) return false;
+    return (cin == 1 && cout == 64) || (chan(cin) && chan(cout));
+}
+static size_t conv_seam_weight_bytes(int precision, int cin, int cout) {
+    const size_t one = cin == 1 ? (size_t)64 * 9 * 4 : (size_t)9 * cin * cout * (precision == 0 ? 2 : 4);
+    return (one + 255) / 256 * 256;
+}
+static bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+size_t mst::seam_conv3x3_workspace_bytes(int32_t precision, int32_t cin, int32_t cout) {
+    if (!conv_seam_shape(precision, 1, 1, 1, cin, cout)) return 0;
+    return (cin == 1 ? 1 : 2) * conv_seam_weight_bytes(precision, cin, cout);
+}
+size_t mst::seam_conv3x3_splitk_bytes(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dgrad) {
+    if (!conv_seam_shape(0, n, h, w, cin, cout) || cin == 1) return 0;
+    return dgrad ? conv_splitk_bytes(n, h, w, cout, cin) : conv_splitk_bytes(n, h, w, cin, cout);
+}
+size_t mst::seam_conv3x3_part_bytes(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dgrad) {
+    if (!conv_seam_shape(0, n, h, w, cin, cout) || (cin == 1 && dgrad)) return 0;
+    return (size_t)conv_pixel_tiles(n, h, w) * (dgrad ? cin : cout) * 2 * sizeof(float);
+}
+template <typename T>
+static int conv_seam_run(int precision, int dgrad, const void* x, const float* weight, void* out, float* part, int32_t* tiles, int n, int h, int w,
+                         int cin, int cout, char* ws, float* splitk, size_t splitk_bytes, hipStream_t s) {
+    int t;
+    if (cin == 1) {
+        float* w1 = (float*)ws;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prep_weights<float>), dim3(3), dim3(256), 0, s, weight, w1, (float*)nullptr, 1, 64);
+        const int64_t P = (int64_t)n * h * w;
+        t = (int)((P + kConv1Pix - 1) / kConv1Pix);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv1<T>), dim3(t), dim3(256), 0, s, (const float*)x, (const float*)w1, (T*)out, part, n, h, w);
+    } else {
+        T* wf = (T*)ws;
+        T* wd = (T*)(ws + conv_seam_weight_bytes(precision, cin, cout));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prep_weights_tiled<T>), dim3(cin / 32, cout / 32), dim3(256), 0, s, weight, wf, wd, cin, cout);
+        ConvArgs ca{x, dgrad ? (const void*)wd : (const void*)wf, out, part, n, h, w, dgrad ? cout : cin, dgrad ? cin : cout, 0, nullptr};
+        t = launch_conv3x3(precision, ca, s, splitk, splitk_bytes);
+    }
+    if (tiles) *tiles = t;
+    return (int)hipGetLastError();
+}
+int mst::seam_conv3x3(int32_t precision, int32_t dgrad, const void* x, const float* weight, void* out, float* part, int32_t* tiles, int32_t n,
+                           int32_t h, int32_t w, int32_t cin, int32_t cout, void* workspace, size_t workspace_bytes, void* splitk,
+                           size_t splitk_bytes, void* stream) {
+    if (!conv_seam_shape(precision, n, h, w, cin, cout) || (cin == 1 && dgrad) || !x || !weight || !out || !workspace ||
+        workspace_bytes < seam_conv3x3_workspace_bytes(precision, cin, cout) || !aligned_to(workspace, 256) || !aligned_to(x, 16) ||
+        !aligned_to(weight, 16) || !aligned_to(out, 16) || !aligned_to(part, 16) || !aligned_to(splitk, 16))
+        return hipErrorInvalidValue;
+    if (precision == 0)
+        return conv_seam_run<bf16_t>(precision, dgrad, x, weight, out, part, tiles, n, h, w, cin, cout, (char*)workspace, (float*)splitk, splitk_bytes,
+                                     (hipStream_t)stream);
+    return conv_seam_run<float>(precision, dgrad, x, weight, out, part, tiles, n, h, w, cin, cout, (char*)workspace, (float*)splitk, splitk_bytes,
+                                (hipStream_t)stream);
+}
+size_t mst::seam_conv_wgrad_workspace_bytes(int32_t precision, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout) {
+    if (!conv_seam_shape(precision, n, h, w, cin, cout)) return 0;
+    int splits, steps;
+    return (size_t)wgrad_part_floats(precision, w, (int64_t)n * h * w, cin, cout, &splits, &steps) * sizeof(float);
+}
+int mst::seam_conv_wgrad(int32_t precision, const void* dy, const void* x, float* grad_weight, int32_t n, int32_t h, int32_t w, int32_t cin,
+                              int32_t cout, void* workspace, size_t workspace_bytes, int32_t* splits, int32_t* steps_per_split, void* stream) {
+    if (!conv_seam_shape(precision, n, h, w, cin, cout) || !dy || !x || !grad_weight || !workspace || !aligned_to(workspace, 256) ||
+        !aligned_to(dy, 16) || !aligned_to(x, 16) || !aligned_to(grad_weight, 16))
+        return hipErrorInvalidValue;
+    int sp, st;
+    const size_t need = (size_t)wgrad_part_floats(precision, w, (int64_t)n * h * w, cin, cout, &sp, &st) * sizeof(float);
+    if (workspace_bytes < need) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    float* wgpart = (float*)workspace;
+    WgradArgs wa{dy, x, wgpart, n, h, w, cin, cout, sp, st};
+    launch_conv_wgrad(precision, wa, s);
+    if (cin == 1) hipLaunchKernelGGL(k_wgrad_reduce_first, dim3(cout), dim3(256), 0, s, wgpart, grad_weight, cout, sp);
+    else hipLaunchKernelGGL(k_wgrad_reduce, dim3(ew_grid((int64_t)cout * (cin / 64) * 256)), dim3(256), 0, s, wgpart, grad_weight, cin, cout, sp);
+    if (splits) *splits = sp;
+    if (steps_per_split) *steps_per_split = st;
+    return (int)hipGetLastError();
+}

@@ -272,6 +272,14 @@ SIGNATURES = {
     "mst_cnn14_forward_sync": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, _P, _P, C.c_size_t, _S, SYNC_FN, _S]),
     "mst_cnn14_backward_sync": (STATUS, [C.POINTER(Cnn14Desc), _P, C.POINTER(Cnn14Params), _P, C.POINTER(Cnn14Grads), _P, C.c_size_t, _S,
                                         SYNC_FN, _S]),
+    "mst_conv3x3_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "mst_conv3x3_splitk_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mst_conv3x3_part_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mst_conv3x3": (STATUS, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                             C.c_int32, _P, C.c_size_t, _P, C.c_size_t, _S]),
+    "mst_conv_wgrad_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mst_conv_wgrad": (STATUS, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), _S]),
     "mst_afloss_backward": (STATUS, [_P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_size_t, _S]),
     "mst_af_profile_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "mst_af_profile": (STATUS, [_P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_size_t, _S]),

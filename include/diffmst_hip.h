@@ -775,6 +775,32 @@ int mst_cnn14_backward_sync(const mst_cnn14_desc* d, const float* spec, const ms
                             const mst_cnn14_grads* grads, void* workspace, size_t workspace_bytes, void* stream, mst_sync_fn sync,
                             void* user);
 
+/* ---- One convolution of the encoder at a time (the seam of tests/test_conv_routes_gpu.py; DESIGN.md "The encoder's convolutions
+ * per route").  Each entry runs, for one layer, exactly what mst_cnn14_forward / _backward run for it: the weight preparation, the
+ * launcher (which chooses the kernel from the shape), and the fold of the partial results.  Images are NHWC in the transposed convention
+ * of the network (h = frames, w = bins); weights and weight gradients are fp32 in torch's layout (cout, cin, 3, 3).  Activations are of
+ * the storage type of `precision` (mst_cnn14_desc::precision): bf16 for 0, fp32 for 1 / 2 / 3.  cin and cout are powers of two in
+ * 64 .. 2048, or cin = 1 with cout = 64 (the first layer: its input is the fp32 (n, h, w) spectrogram whatever the precision, and it
+ * has no data gradient).  Every pointer is a device pointer aligned to 16 bytes, workspaces to 256. */
+/* the two operand layouts of the prepared weights */
+size_t mst_conv3x3_workspace_bytes(int32_t precision, int32_t cin, int32_t cout);
+/* what the split-K route of this shape needs; 0: the shape is never split.  dgrad = 1: the data gradient (channel roles swapped) */
+size_t mst_conv3x3_splitk_bytes(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dgrad);
+/* room for the per-tile statistics of any route: (tiles, channels of the result, 2) fp32 with the smallest tile */
+size_t mst_conv3x3_part_bytes(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t dgrad);
+/* dgrad = 0: x (n, h, w, cin) -> out (n, h, w, cout); dgrad = 1: x is the cotangent (n, h, w, cout) -> out (n, h, w, cin).
+ * part: NULL, or the per-tile sum / sum of squares of the fp32 results, (tiles, channels of out, 2); *tiles (host, may be NULL) gets
+ * the tile count.  splitk: NULL (or too small) takes the unsplit route. */
+int mst_conv3x3(int32_t precision, int32_t dgrad, const void* x, const float* weight, void* out, float* part, int32_t* tiles, int32_t n,
+                int32_t h, int32_t w, int32_t cin, int32_t cout, void* workspace, size_t workspace_bytes, void* splitk, size_t splitk_bytes,
+                void* stream);
+/* the partial sums of the split the network chooses for this shape */
+size_t mst_conv_wgrad_workspace_bytes(int32_t precision, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout);
+/* dy (n, h, w, cout), x (n, h, w, cin) -> grad_weight (cout, cin, 3, 3) fp32, overwritten.  *splits / *steps_per_split (host, may be
+ * NULL) get the pixel split that ran (steps of 32 pixels). */
+int mst_conv_wgrad(int32_t precision, const void* dy, const void* x, float* grad_weight, int32_t n, int32_t h, int32_t w, int32_t cin,
+                   int32_t cout, void* workspace, size_t workspace_bytes, int32_t* splits, int32_t* steps_per_split, void* stream);
+
 /* ---- TransformerController encoder stack (reference mst/modules.py:848-854, :893-895: torch.nn.TransformerEncoder of
  * post-norm TransformerEncoderLayer(d_model, nhead, dim_feedforward, relu, dropout 0, batch_first) over the (bs, seq, d_model)
  * token sequence, with the key-padding mask of :880-890).  fp32 operands on v_mfma_f32_16x16x4_f32.  Limits: seq <= 128,
